@@ -10,13 +10,20 @@ one kept sample per chain (i.e. one row block of the reference's mcmc() output).
 chain states are resident in HBM before the timed region starts.
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  Multi-GPU: chains are sharded (weak scaling: 4096 per GPU, the
 Philox counter carries the global chain id) and the kept samples are gathered to rank 0 over
 RCCL inside the timed region.
 
-At N = 1 the line also carries, outside the timed region:
+A plain run sets up, pre-warms, runs the W warm-up and the N timed steps and prints the headline line; nothing else.
+The time-bounded pre-warm runs on a chain set of its own, so the timed chains have seen exactly W + N launches: with
+the same arguments the timed steps compute the same samples on any machine.  `--dump-outputs DIR` writes the last
+timed step's kept samples (every chain, after the gather at N > 1) to DIR/samples.npy (float32 [chains, p]; a fixed
+seeded sample of the chains above 64 MB).
+
+With `--full` (at N = 1) the line also carries, outside the timed region:
   cpu_baseline   the float64 C oracle (OpenMP over chains) on a bounded sample of the same workload ("port")
   reference_cpu  the reference's own NumPy script, as measured in BASELINE.md (1 core)
   ess            ESS per kept draw from a separate 512-draw run (Geyer), scaled to the timed throughput
@@ -25,6 +32,9 @@ At N = 1 the line also carries, outside the timed region:
                  dmm=1/pre) at 4096 chains with like-for-like it/s and min-ESS/s
   extra.f64      the headline workload on the float64 instantiation (the reference computes in float64)
   extra.f64_wide config 5's shape on a float64 model (f64 matrix pipe)
+At N > 1, `--full` adds rank 0's bit-exact re-run of another rank's block (`multi_gpu.gather_bitexact`) and BASELINE
+configs 3 and 5 across the ranks (`extra.configs`).  `--no-cpu-baseline`, `--no-ess`, `--no-extra` and `--host-boundary`
+select within `--full`.
 
 `--dry-run` exercises the launch plumbing without a GPU (gloo instead of RCCL, no kernels): rank/world parsing,
 shard offsets, the gather and the max-over-ranks reduction -- what tests/test_host_logic.py runs on CPU.
@@ -753,6 +763,21 @@ def headline_init(rank, C):
     return INIT + 0.1 * 0.17 * rng.standard_normal((C, N_PAR))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, samples):
+    """`--dump-outputs`: the last timed step's kept samples [chains, p] as path/samples.npy, float32.  Above DUMP_MAX_BYTES a
+    fixed seeded sample of the chains (in chain order) is written instead, so that two builds' dumps compare row for row."""
+    samples = np.ascontiguousarray(samples, dtype=np.float32)
+    max_rows = DUMP_MAX_BYTES // (samples.shape[1] * samples.itemsize)
+    if samples.shape[0] > max_rows:
+        keep = np.sort(np.random.Generator(np.random.Philox(SEED)).choice(samples.shape[0], size=max_rows, replace=False))
+        samples = samples[keep]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "samples.npy"), samples)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` as a PLAIN process (no WORLD_SIZE / RANK in the environment), N > 1: start the N ranks
     ourselves -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>
@@ -785,16 +810,21 @@ def main(argv=None):
     ap.add_argument("--precision", default="full", choices=["full", "auto", "bf16"],
                     help="headline run: 'full' = every gradient evaluation in fp32 (the default: `value` is an all-fp32 number); "
                          "'auto' = the library's default policy (HMC interior gradients on the bf16 matrix pipe)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ess", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs 1/3/4/5 sub-results")
-    ap.add_argument("--host-boundary", action="store_true", help="also time the headline through mcmc(): host array in, host samples out (PCIe inclusive)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: CPU baseline, ESS, the "
+                    "other configurations, precisions and dtypes (N = 1); the gather re-run check and configs 3 / 5 across the ranks (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's kept samples to DIR/samples.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ess", action="store_true", help="with --full: skip the ESS run")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the configs 1/3/4/5 sub-results")
+    ap.add_argument("--host-boundary", action="store_true", help="with --full: also time the headline through mcmc(): host array in, host samples out (PCIe inclusive)")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (gloo, no GPU work)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (gloo: the CPU tests)")
     ap.add_argument("--scale", type=int, default=1, help="divide the chain counts / run lengths of the multi-GPU configs 3 and 5 "
                     "(CPU tests only; rows are marked scaled_down)")
     ap.add_argument("--prewarm", type=float, default=PREWARM_S, help="seconds of untimed load before the warm-up steps")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         return self_launch(a.gpus)
@@ -830,20 +860,24 @@ def main(argv=None):
     plan = cs.plan()
     out = la.DeviceArray(dev, (a.steps, C, N_PAR), np.float32)
 
-    def one_step(i, keep):
-        cs.advance(1, THIN, keep=keep, out=out.rows(i % a.steps, i % a.steps + 1))
+    def one_step(chains, i):
+        chains.advance(1, THIN, keep=True, out=out.rows(i % a.steps, i % a.steps + 1))
 
     # Untimed pre-warm: the GPU needs some tens of milliseconds of load before it holds its clocks (measured: the same
     # 50 timed steps run at 0.417-0.424 ms after 5 warm-up steps = 2 ms of load, at 0.389-0.391 ms after 200 or 1000), and
-    # `value` is meant to be the sustained rate whatever W the caller picks.  Same launches as the timed ones.
+    # `value` is meant to be the sustained rate whatever W the caller picks.  Same launches as the timed ones, on a chain set
+    # of their own (same start, same plan): the timed chains see W + N launches whatever the pre-warm's count, so what the
+    # timed steps compute does not depend on how fast the machine is.
+    pre = la.ChainSet(kern, q0, seed=SEED, chain_offset=rank * C, group=a.group, mode=a.mode, stream=stream, precision=a.precision)
     t_pre, n_pre = time.perf_counter(), 0
     while time.perf_counter() - t_pre < a.prewarm:
         for _ in range(20):
-            one_step(n_pre, True)
+            one_step(pre, n_pre)
             n_pre += 1
-        cs.sync()
+        pre.sync()
+    del pre
     for i in range(a.warmup):
-        one_step(i, True)
+        one_step(cs, i)
     cs.sync()
 
     timer = Timer(L, _lib.check, dev, stream)
@@ -854,7 +888,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     timer.start()
     for i in range(a.steps):
-        one_step(i, True)
+        one_step(cs, i)
     _lib.check(L.lr_event_record(dev, timer.e1, stream))
     cs.sync()
     gather_s, gathered = ex.gather(tout, out)  # the ONE exchange of the path: RCCL gather of the thinned samples to rank 0
@@ -869,13 +903,11 @@ def main(argv=None):
 
     check_block = None
     if ex.active:
-        launches_before = ex.all_gather_i64(n_pre + a.warmup)  # the pre-warm is time-bounded: every rank's own count
-
         def rerun(r):
             k = min(CHECK_CHAINS, C)
             c2 = la.ChainSet(kern, headline_init(r, C)[:k], seed=SEED, chain_offset=r * C, group=a.group, mode=a.mode,
                              stream=stream, precision=a.precision, plan_chains=C, plan_first=r * C)
-            for _ in range(launches_before[r]):
+            for _ in range(a.warmup):  # (every rank's timed chains saw the W warm-up launches; the pre-warm had chains of its own)
                 c2.advance(1, THIN, keep=False)
             buf = la.DeviceArray(dev, (a.steps, k, N_PAR), np.float32)
             for i in range(a.steps):
@@ -884,9 +916,13 @@ def main(argv=None):
             res = buf.to_host()
             buf.free()
             return res
-        check_block = self_check(ex, _lib.device_info(dev), kernel_ms_total / a.steps, gathered, min(1, world - 1), rerun)
+        check_block = self_check(ex, _lib.device_info(dev), kernel_ms_total / a.steps, gathered, min(1, world - 1),
+                                 rerun if a.full else None)
+    if rank == 0 and a.dump_outputs:  # (before dist_configs: its gathers may reuse the receive buffers of this block shape)
+        last = [g[-1].cpu().numpy() for g in gathered] if gathered is not None else [out.rows(a.steps - 1, a.steps).to_host()[0]]
+        dump_outputs(a.dump_outputs, np.concatenate(last, axis=0))
     dist_rows = None
-    if ex.active and not a.no_extra:
+    if ex.active and a.full and not a.no_extra:
         dist_rows = dist_configs(la, L, _lib.check, dev, stream, ex, rank, world, a.scale)
 
     if rank == 0:
@@ -908,7 +944,7 @@ def main(argv=None):
             # the exchange's share of the timed region (max over ranks; 0 without a process group): separates compute from
             # the gather in a 1 -> 8 GPU curve
             "gather_ms": gather_s * 1e3,
-            "prewarm": {"seconds": a.prewarm, "steps": n_pre, "note": "untimed launches before the W warm-up steps, until the GPU holds its clocks"},
+            "prewarm": {"seconds": a.prewarm, "steps": n_pre, "note": "untimed launches before the W warm-up steps, until the GPU holds its clocks (on chains of their own)"},
             "higher_is_better": True,
             "scaling": "weak",
             # BASELINE.md's number for this metric: the reference's own fit-np-hmc.py, 1 368 it/s x 1 chain (1 core)
@@ -973,7 +1009,7 @@ def main(argv=None):
                     break
             except (OSError, KeyError, ValueError):
                 pass
-        if not a.no_ess:
+        if a.full and not a.no_ess:
             eff, shape, ess_plan = ess_per_draw(la, model, kern, q0, dev, plan, a.precision)
             draws_per_s = world * C * a.steps / wall
             line["min_ess_per_s"] = float(eff.min() * draws_per_s)
@@ -989,7 +1025,7 @@ def main(argv=None):
         if dist_rows is not None:
             # N > 1 (or the forced one-rank process group): BASELINE configs 3 and 5 as stated, across the ranks
             line["extra"] = {"configs": dist_rows}
-        elif world == 1 and not a.no_extra:
+        elif world == 1 and a.full and not a.no_extra:
             f64 = f64_run(la, L, _lib.check, dev, stream, X, y, pscale, q0, a.steps)
             # TOP LEVEL: the same workload in the reference's own arithmetic (Python/fit-np-hmc.py:17-19 computes in float64; `value`
             # above is the float32 instantiation the contract prescribes) -- HIP-event timed, same chains, same launches
@@ -1019,7 +1055,7 @@ def main(argv=None):
             line["teardown_error"] = repr(e)[:300]
     if rank == 0:
         try:
-            if not a.no_cpu_baseline:
+            if a.full and not a.no_cpu_baseline:
                 line["cpu_baseline"] = cpu_baseline(X, y, pscale, init)
         except Exception as e:  # noqa: BLE001
             line["cpu_baseline"] = {"error": repr(e)[:300]}

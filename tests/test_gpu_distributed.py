@@ -47,7 +47,7 @@ def _bench(extra_env, *launcher, extra=False):
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, *launcher, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "1",
-           "--no-ess", "--no-cpu-baseline"] + ([] if extra else ["--no-extra"])
+           "--no-ess", "--no-cpu-baseline"] + (["--full"] if extra else ["--no-extra"])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -73,8 +73,8 @@ def test_bench_rccl_branch_runs_on_a_gpu_under_torchrun():
         # does guard the kernel -- the wall-clock comparisons below are sanity factors only
         assert d["roofline"]["kernel_ms"] < 0.48 and d["roofline"]["frac"] > 0.40, d["roofline"]
     assert dist["config"]["parallelism"] == "chains sharded x1" and dist["gather_ms"] > 0 and plain["gather_ms"] == 0
-    # (same seed and chain ids; the timed window starts after a TIME-bounded pre-warm, so the two runs may sit 20 launches apart in the
-    #  chains' history -- equal to the Monte-Carlo error of 3.3e6 proposals, not to the bit: round 6 saw 0.92223 against 0.92232)
+    # (same seed and chain ids; the TIME-bounded pre-warm runs on chains of its own, so both timed windows start after the same W
+    #  launches -- equal to the Monte-Carlo error of 3.3e6 proposals at least)
     assert abs(dist["accept_rate"] - plain["accept_rate"]) < 2e-3, (dist["accept_rate"], plain["accept_rate"])
     # 40 timed steps = 15 ms (round 5; with 5 steps = 2 ms the closing RCCL barrier alone, inside the timed region, decided the
     # comparison): the gather (5 MB device-to-device at N = 1) is inside the timed region of the distributed run
@@ -107,14 +107,14 @@ def test_bench_rccl_branch_runs_on_a_gpu_under_torchrun():
 
 def test_bench_with_two_ranks_sharing_the_gpu_over_gloo():
     """The N = 2 flow of bench.py with real kernels in BOTH ranks: two processes under torch.distributed.run on the one GPU of a test
-    box, the exchange on gloo (RCCL refuses two ranks on one device).  Rank 1's chain block (chain_offset = C, its own pre-warm count),
+    box, the exchange on gloo (RCCL refuses two ranks on one device).  Rank 1's chain block (chain_offset = C),
     the gather, and the line's self-check: rank 0 re-runs 64 chains of RANK 1's block and finds them bit-equal; the line says the two
     ranks shared a device."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "6",
-           "--warmup", "2", "--no-ess", "--no-cpu-baseline", "--scale", "8"]
+           "--warmup", "2", "--no-ess", "--no-cpu-baseline", "--scale", "8", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

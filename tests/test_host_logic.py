@@ -224,7 +224,7 @@ def test_bench_multi_gpu_line_on_the_abi_test_double(world):
     being the CPU test double (tests/bench_on_twin.py injects it; chain counts scaled down 64x, marked in the rows)."""
     import os
     d = _torchrun(world, os.path.join(REPO, "tests", "bench_on_twin.py"), "--gpus", str(world), "--chains", "80", "--steps", "2",
-                  "--warmup", "1", "--prewarm", "0.02", "--scale", "64")
+                  "--warmup", "1", "--prewarm", "0.02", "--scale", "64", "--full")
     assert d["n_gpus"] == world and d["config"]["chains_per_gpu"] == 80 and d["value"] > 0 and d["gather_ms"] > 0
     mg = d["multi_gpu"]
     assert mg["ranks_seen"] == world and len(mg["devices"]) == world and mg["devices_distinct"]
@@ -262,7 +262,7 @@ def test_bench_gpus_n_without_a_launcher_starts_its_own_ranks():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "bench_on_twin.py"), "--gpus", "2", "--chains", "80", "--steps", "2",
-                        "--warmup", "1", "--prewarm", "0.02", "--scale", "64"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--prewarm", "0.02", "--scale", "64", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     assert "without a launcher: starting 2 ranks" in r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -271,6 +271,36 @@ def test_bench_gpus_n_without_a_launcher_starts_its_own_ranks():
     assert d["n_gpus"] == 2 and d["multi_gpu"]["ranks_seen"] == 2 and d["multi_gpu"]["gather_bitexact"] is True
     assert {row["config"] for row in d["extra"]["configs"]} == {3, 5}
 
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_whatever_the_prewarm(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` (the real main() on the ABI test double) times N steps and prints the headline
+    line without the --full measurements; --dump-outputs writes the last timed step's kept samples.  The pre-warm runs on chains of
+    its own, so two runs whose time-bounded pre-warms differ (none, and one batch of 20 launches) dump identical samples."""
+    import json
+    import os
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines, dumps = [], []
+    for i, prewarm in enumerate(("0", "0.001")):
+        out = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "bench_on_twin.py"), "--gpus", "1", "--chains", "16", "--steps", "3",
+                            "--warmup", "1", "--prewarm", prewarm, "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1
+        lines.append(json.loads(js[0]))
+        assert sorted(os.listdir(out)) == ["samples.npy"]
+        dumps.append(np.load(out / "samples.npy"))
+    assert [d["prewarm"]["steps"] for d in lines] == [0, 20]
+    for d in lines:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "chain-iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] == pytest.approx(16 * 3 * 20 / (3 * d["ms_per_step"] / 1e3), rel=1e-9)
+        assert not {"extra", "ess", "min_ess_per_s", "cpu_baseline", "reference_arithmetic", "host_boundary"} & set(d)
+    assert dumps[0].shape == (16, 8) and dumps[0].dtype == np.float32 and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 def test_bench_refuses_more_ranks_than_gpus():
     """`--gpus 2` over RCCL on a node with fewer than 2 GPUs (this container has none): the ranks refuse before the rendezvous

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 passes of ONE command on the GPU box (via gpurun): a kernel trace and separate PMC passes (never combined).
 #   tools/gpu_profile.sh <outdir-name> [--pmc-only|--trace-only] -- python3 <script> [args...]
-# default command: python3 bench.py --no-cpu-baseline --no-ess   (the round's profile of record: tools/refresh_profiles.py <tag>)
+# default command: python3 bench.py --full --no-cpu-baseline --no-ess   (the round's profile of record: tools/refresh_profiles.py <tag>)
 # Writes gpurun_out/<outdir-name>/summary.txt (tools/summarize_prof.py) and bench_line.json when the command printed a JSON line;
 # the rocpd databases (tens of MB per pass; gpurun merges at most 64 MiB back) are deleted.
 set -u
@@ -11,7 +11,7 @@ NAME=${1:-prof}; shift || true
 WHAT=all
 case "${1:-}" in --pmc-only) WHAT=pmc; shift;; --trace-only) WHAT=trace; shift;; esac
 [ "${1:-}" = "--" ] && shift
-if [ $# -eq 0 ]; then set -- python3 $ROOT/bench.py --no-cpu-baseline --no-ess; fi
+if [ $# -eq 0 ]; then set -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-ess; fi
 OUT=$ROOT/gpurun_out/$NAME
 mkdir -p $OUT
 export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Copy the summaries of a tools/gpu_profile.sh run of bench.py (gpurun_out/<dir>) into profiles/ (tracked).
 usage: refresh_profiles.py <tag> gpurun_out/<dir>      e.g.  refresh_profiles.py r5 gpurun_out/prof_r5
-Writes profiles/<tag>_rocprof_summary.txt (kernel trace + PMC passes of `python3 bench.py --no-cpu-baseline --no-ess`),
+Writes profiles/<tag>_rocprof_summary.txt (kernel trace + PMC passes of `python3 bench.py --full --no-cpu-baseline --no-ess`),
 profiles/<tag>_traffic.json (HBM bytes per launch of the headline kernel, for bench.py's roofline.traffic) and
 profiles/<tag>_bench_line_profiled.json (the bench line of the traced run)."""
 import json, os, re, shutil, sys
@@ -23,7 +23,7 @@ def counter(name, kernel_pat):
 
 kpat = r"k_chain<float, 8, 16, 0, 13, 2>"
 f, w = counter("FETCH_SIZE", kpat), counter("WRITE_SIZE", kpat)
-t = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --no-cpu-baseline --no-ess`, "
+t = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `python3 bench.py --full --no-cpu-baseline --no-ess`, "
                "" + f"{tag} (tools/gpu_profile.sh; profiles/{tag}_rocprof_summary.txt)",
      "kernel": "lr::k_chain<float, 8, 16, 0, 13, 2>", "kernel_variant": d["config"]["kernel_variant"],
      "chains": d["config"]["chains_per_gpu"], "thin": d["config"]["thin"],

@@ -8,7 +8,7 @@ import sys
 
 src, dst = sys.argv[1], sys.argv[2]
 cmd_file = os.path.join(src, "command.txt")
-cmd = open(cmd_file).read().strip() if os.path.exists(cmd_file) else "python3 bench.py --no-cpu-baseline --no-ess"
+cmd = open(cmd_file).read().strip() if os.path.exists(cmd_file) else "python3 bench.py --full --no-cpu-baseline --no-ess"
 lines = [f"# rocprofv3 summary of `{cmd}` ({os.path.basename(src)})",
          "# produced by tools/gpu_profile.sh on one MI355X; kernel-trace and each --pmc set are separate runs", ""]
 dbs = glob.glob(os.path.join(src, "trace", "**", "*_results.db"), recursive=True)
