@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(HERE, "lib", "liblogreg_hip.so")
 LR_F32, LR_F64 = 0, 1
 STATS_ROWS = 7  # LR_STATS_ROWS
 PREC_BY_NAME = {"auto": 0, "full": 1, "bf16": 2}  # LR_PREC_*
-KIND_BY_NAME = {"rwmh": 0, "mala": 1, "hmc": 2, "ul": 3}  # LR_KIND_*
+KIND_BY_NAME = {"rwmh": 0, "mala": 1, "hmc": 2, "ul": 3, "nuts": 4}  # LR_KIND_* (LR_KIND_NUTS: include/logreg_hip_nuts.h)
+NUTS_MAX_DEPTH = 10  # LR_NUTS_MAX_DEPTH
 MODE_AUTO, MODE_REG, MODE_LDS, MODE_GLOBAL, MODE_MFMA, MODE_STEPWISE, MODE_MIXED = -1, 0, 1, 2, 3, 4, 5
 MODE_NAMES = {MODE_REG: "reg", MODE_LDS: "lds", MODE_GLOBAL: "global", MODE_MFMA: "mfma", MODE_STEPWISE: "stepwise", MODE_MIXED: "mixed"}
 MODE_BY_NAME = {"auto": MODE_AUTO, "reg": MODE_REG, "lds": MODE_LDS, "global": MODE_GLOBAL, "mfma": MODE_MFMA, "stepwise": MODE_STEPWISE, "mixed": MODE_MIXED}
@@ -82,7 +83,38 @@ SYMBOLS = {
     "lr_allreduce_sum_f64": (C.c_int, [_vp, _vp, _u64, _vp]),
 }
 
+
+class NutsCounters(C.Structure):  # lr_nuts_counters (include/logreg_hip_nuts.h)
+    _fields_ = [("n_leapfrog", C.c_uint64), ("depth_sum", C.c_uint64), ("accept_stat_sum", C.c_double), ("divergent", C.c_uint32),
+                ("max_depth_hits", C.c_uint32)]
+
+
+# name -> (restype, argtypes); every symbol include/logreg_hip_nuts.h declares.  A table of its own, bound on first use (load_nuts):
+# SYMBOLS is the exact symbol set of logreg_hip.h
+NUTS_SYMBOLS = {
+    "lr_run_nuts": (C.c_int, [_vp, _vp, C.c_double, _i32, _vp, _op, _vp, _vp, _vp]),
+}
+
 _lib = None
+_nuts = None
+
+
+def bind_nuts(L):
+    """`L` (a loaded library handle) with the NUTS entry points bound; resolved once per handle."""
+    global _nuts
+    if _nuts is L:
+        return L
+    for name, (res, args) in NUTS_SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+        fn.restype = res
+        fn.argtypes = args
+    _nuts = L
+    return L
+
+
+def load_nuts():
+    """The library with the NUTS entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_nuts(load())
 
 
 def load():

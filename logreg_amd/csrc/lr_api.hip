@@ -4,6 +4,7 @@
 //   lr_engine.h  kernel argument packing, workspaces, the stepwise driver   lr_inst*.hip the launches, one unit per (dtype, width)
 // All arithmetic of the path runs in the kernels (lr_kernels.h, lr_mfma.h, lr_tall*.h, lr_wide*.h).
 #include "../../include/logreg_hip.h"
+#include "../../include/logreg_hip_nuts.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -17,6 +18,7 @@
 
 #include "lr_inst.h"
 #include "lr_kernels.h"
+#include "lr_nuts.h"
 #include "lr_hessian.h"
 #include "lr_mfma.h"
 #include "lr_stats.h"
@@ -111,6 +113,42 @@ int run_common(lr_model* m, const RunSpec& rs, const lr_run_opts* o, void* state
     if (out) LR_HIP(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
     if (accepts) LR_HIP(hipMemcpy(accepts, dacc.p, o->n_chains * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return LR_OK;
+}
+
+static_assert(sizeof(lr::NutsCounters) == sizeof(lr_nuts_counters), "lr_nuts_counters layout");
+
+template <typename T, int P>
+int do_nuts_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
+              void* out, lr_nuts_counters* counters, int8_t* depth_out) {
+    auto ma = model_args<T, P>(m);
+    lr::NutsArgs<T, P> na{};
+    na.state = static_cast<T*>(state);
+    na.out = static_cast<T*>(out);
+    na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
+    na.depth_out = depth_out;
+    na.C = o->n_chains;
+    na.chain_offset = o->chain_offset;
+    na.iters = o->iters;
+    na.thin = o->thin;
+    na.iter_offset = o->iter_offset;
+    na.seed = o->seed;
+    na.p = m->p;
+    na.max_depth = max_depth;
+    na.step = (T)eps;
+    for (int j = 0; j < P; ++j) {  // sqrt(dmm), eps / dmm, 1 / dmm; zero in padded coordinates
+        na.a[j] = j < m->p ? (T)std::sqrt(dmm[j]) : T(0);
+        na.b[j] = j < m->p ? (T)(eps / dmm[j]) : T(0);
+        na.c[j] = j < m->p ? (T)(1.0 / dmm[j]) : T(0);
+    }
+    na.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const int rc = m->table->launch_nuts(&cfg, o->n_chains, &ma, &na);
+    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return LR_OK;
+}
+int do_nuts(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
+            void* out, lr_nuts_counters* counters, int8_t* depth_out) {
+    LR_DISPATCH_TP(m, do_nuts_t, m, pl, st, o, eps, max_depth, dmm, state, out, counters, depth_out);
 }
 
 int positive_vec(const char* name, const double* v, int p) {
@@ -389,10 +427,11 @@ int lr_plan_run_info(const lr_model* m, int32_t kind, const lr_run_opts* o, lr_p
     if (!out) return fail(LR_ERR_INVALID, "out is NULL");
     int rc = check_opts(m, o, false);
     if (rc) return rc;
-    if (kind < LR_KIND_RWMH || kind > LR_KIND_UL) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
+    if (kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
     Plan pl;
-    rc = make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
-                   o->precision == LR_PREC_AUTO);
+    rc = kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, LR_NUTS_MAX_DEPTH, &pl)
+                              : make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
+                                          o->precision == LR_PREC_AUTO);
     if (rc) return rc;
     *out = lr_plan_info{pl.mode, pl.G, pl.R, pl.G2, pl.R2, pl.split, pl.mode2, 0};
     return LR_OK;
@@ -401,10 +440,11 @@ int lr_plan_run_info(const lr_model* m, int32_t kind, const lr_run_opts* o, lr_p
 int lr_plan_run(const lr_model* m, int32_t kind, const lr_run_opts* o, int32_t* mode_out, int32_t* group_out, int32_t* rows_out) {
     int rc = check_opts(m, o, false);
     if (rc) return rc;
-    if (kind < LR_KIND_RWMH || kind > LR_KIND_UL) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
+    if (kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
     Plan pl;
-    rc = make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
-                   o->precision == LR_PREC_AUTO);
+    rc = kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, LR_NUTS_MAX_DEPTH, &pl)
+                              : make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
+                                          o->precision == LR_PREC_AUTO);
     if (rc) return rc;
     if (mode_out) *mode_out = pl.mode;
     if (group_out) *group_out = pl.G;
@@ -498,6 +538,53 @@ int lr_run_hmc(lr_model* m, void* state, double eps, int32_t l, const double* dm
         rs.c[j] = 1.0 / dmm[j];
     }
     return run_common(m, rs, o, state, nullptr, out, accepts);
+}
+
+// NUTS (include/logreg_hip_nuts.h; fit-blackjax-nuts.py:101, fit-numpyro.py:36-46).  opts->precision is read as FULL, lp_state does not
+// exist, the run is one part (plan_nuts).
+int lr_run_nuts(lr_model* m, void* state, double eps, int32_t max_depth, const double* dmm, const lr_run_opts* o, void* out,
+                lr_nuts_counters* counters, int8_t* depth_out) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
+    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
+    int rc = positive_vec("dmm", dmm, m->p);
+    if (rc) return rc;
+    rc = check_opts(m, o, true);
+    if (rc) return rc;
+    if (!state) return fail(LR_ERR_INVALID, "state is NULL");
+    LR_HIP(hipSetDevice(m->device));
+    Plan pl;
+    rc = plan_nuts(m, o->group, o->mode, max_depth, &pl);
+    if (rc) return rc;
+    if (o->iters == 0) return LR_OK;
+    if (o->on_device) return do_nuts(m, pl, (hipStream_t)o->stream, o, eps, max_depth, dmm, state, out, counters, depth_out);
+
+    const int64_t C = o->n_chains;
+    const size_t sbytes = (size_t)C * m->p * m->esize();
+    const size_t obytes = out ? (size_t)o->iters * C * m->p * m->esize() : 0;
+    const size_t cbytes = counters ? (size_t)C * sizeof(lr_nuts_counters) : 0;
+    const size_t dbytes = depth_out ? (size_t)o->iters * C : 0;
+    const size_t stbytes = o->stats ? (size_t)o->stats_slots * C * 2 * m->p * sizeof(double) : 0;
+    DevBuf ds, dout, dcnt, ddep, dstats;
+    if (ds.alloc(sbytes) || dout.alloc(obytes) || dcnt.alloc(cbytes) || ddep.alloc(dbytes) || dstats.alloc(stbytes))
+        return fail(LR_ERR_NOMEM, "device allocation failed (%zu bytes of samples)", obytes);
+    lr_run_opts od = *o;
+    if (o->stats) {
+        LR_HIP(hipMemcpy(dstats.p, o->stats, stbytes, hipMemcpyHostToDevice));
+        od.stats = static_cast<double*>(dstats.p);
+    }
+    LR_HIP(hipMemcpy(ds.p, state, sbytes, hipMemcpyHostToDevice));
+    if (counters) LR_HIP(hipMemcpy(dcnt.p, counters, cbytes, hipMemcpyHostToDevice));
+    rc = do_nuts(m, pl, nullptr, &od, eps, max_depth, dmm, ds.p, out ? dout.p : nullptr, counters ? (lr_nuts_counters*)dcnt.p : nullptr,
+                 depth_out ? (int8_t*)ddep.p : nullptr);
+    if (rc) return rc;
+    LR_HIP(hipDeviceSynchronize());
+    if (o->stats) LR_HIP(hipMemcpy(o->stats, dstats.p, stbytes, hipMemcpyDeviceToHost));
+    LR_HIP(hipMemcpy(state, ds.p, sbytes, hipMemcpyDeviceToHost));
+    if (out) LR_HIP(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
+    if (counters) LR_HIP(hipMemcpy(counters, dcnt.p, cbytes, hipMemcpyDeviceToHost));
+    if (depth_out) LR_HIP(hipMemcpy(depth_out, ddep.p, dbytes, hipMemcpyDeviceToHost));
+    return LR_OK;
 }
 
 int lr_hessian(lr_model* m, const double* beta, double* lpost, double* grad, double* hess, void* stream) {

@@ -29,6 +29,8 @@ namespace lr {
 // key = (seed_lo, seed_hi); counter = (chain, iter_lo, iter_hi, block | tag).
 // Normal j of an iteration comes from block j/4: Box-Muller pairs (w0,w1)->(z0,z1),
 // (w2,w3)->(z2,z3).  The accept uniform is word 0 of block tag 0x80000000.
+// NUTS (lr_nuts.h) adds block 0x40000000 | d (doubling d < 16: direction bit, merge uniform) and 0x20000000 | k/4 (leaf uniforms,
+// k < 1023): disjoint from the normal blocks and from TAG_UNIFORM.
 // 24-bit uniforms u = ((w >> 8) + 0.5) * 2^-24 are exact in fp32 and fp64.
 // ------------------------------------------------------------------------------------------
 struct U4 { uint32_t x, y, z, w; };

@@ -71,6 +71,8 @@ struct InstTable {
     // this width) and the one-off build into `store`; may be null
     size_t (*mfma_image_bytes)(int64_t n);
     int (*launch_mfma_image)(hipStream_t, const void* rows, int64_t n, void* store);
+    // NUTS (lr_nuts.h), rows in LDS on 16 lanes per chain; `nuts_args` is a NutsArgs<T,P>; null where no such kernel exists
+    int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
 };
 
 }  // namespace lr

@@ -2,6 +2,7 @@
 // Compiled several times:  hipcc -DLR_T=float -DLR_P=8 -DLR_SFX=f32_p8 -DLR_DTYPE=0 ...
 #include "lr_inst.h"
 #include "lr_kernels.h"
+#include "lr_nuts.h"
 #include "lr_tall.h"
 #if LR_DTYPE == 0 && LR_P >= 8
 #include "lr_mfma.h"
@@ -282,8 +283,16 @@ int launch_tall_update(hipStream_t st, int kind, int phase, int64_t iter, int64_
     return check(hipGetLastError());
 }
 
+// NUTS: one kernel per (dtype, padded p), rows in LDS, 16 lanes per chain (lr_nuts.h); cfg->lds_bytes = rows + checkpoints
+int launch_nuts(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
+    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
+    const auto& a = *static_cast<const NutsArgs<T, P>*>(nuts_args);
+    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
+    return launch_capped<&k_nuts<T, P, MODE_LDS, 0>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
+}
+
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts};
 
 }  // namespace
 }  // namespace lr

@@ -506,6 +506,27 @@ int make_plan(const lr_model* m, int64_t C, int group, int mode, Plan* out, bool
     return LR_OK;
 }
 
+// NUTS (include/logreg_hip_nuts.h): one kernel family, rows in LDS on 16 lanes per chain (lr_nuts.h), planned as ONE part.  Everything
+// else is refused with the reason: wide models, a forced mode or lane count the family does not have, rows and checkpoints beyond the
+// LDS (tall data: the stepwise engine has no NUTS kernel).  The LDS figure is the rows + the U-turn checkpoints at `max_depth`.
+size_t nuts_lds_bytes(const lr_model* m, int max_depth) {
+    return lds_rows_bytes(m) + (size_t)2 * max_depth * ((m->P + 15) / 16) * 256 * m->esize();
+}
+int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out) {
+    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
+    if (mode == LR_MODE_STEPWISE) return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine has no NUTS kernel; NUTS runs with the rows in LDS");
+    if (mode != LR_MODE_AUTO && mode != LR_MODE_LDS)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: mode %d has no NUTS kernel (rows in LDS only: LR_MODE_LDS or LR_MODE_AUTO)", mode);
+    if (group != 0 && group != 16) return fail(LR_ERR_UNSUPPORTED, "NUTS: group %d has no NUTS kernel (16 lanes per chain only)", group);
+    const size_t bytes = nuts_lds_bytes(m, max_depth);
+    if (bytes > kLdsBudget)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes) and the U-turn checkpoints need %zu bytes of LDS, beyond the %zu a "
+                    "workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n, lds_rows_bytes(m), bytes, kLdsBudget);
+    if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
+    *out = Plan{lr::MODE_LDS, 16, 0, bytes};
+    return LR_OK;
+}
+
 // `group` means different things per mode (include/logreg_hip.h): lanes per chain (REG / LDS / GLOBAL / AUTO on narrow models:
 // a power of two <= 64), row-split ways of the matrix-core chain kernel (MFMA: 1, 4, 8), or the slice count of the stepwise
 // engine (STEPWISE, and every mode of a wide model: any positive count up to one slice per 32-row block -- ceil(n / slice_len)

@@ -4,6 +4,7 @@
     malaKernel(lpi, glpi, dt=1e-4, pre=1)        fit-np-mala.py:72-78
     hmcKernel(lpi, glpi, eps=1e-4, l=10, dmm=1)  fit-np-hmc.py:65-87
     ulKernel(glpi, dt=1e-4, pre=1)               fit-np-ul.py:61-68
+    nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10)   blackjax.nuts in fit-blackjax-nuts.py:101 (dmm = 1 / pre)
     mcmc(init, kernel, thin=10, iters=10000, verb=True)   fit-np-hmc.py:89-103
 
 When the callables passed in are the closures of a `LogReg` model (and, for RWMH, a
@@ -28,6 +29,10 @@ import numpy as np
 from . import _lib
 from ._lib import RunOpts, check
 from .model import DeviceArray, LogReg, ModelFn
+
+# lr_nuts_counters (include/logreg_hip_nuts.h) as a NumPy record
+NUTS_COUNTERS = np.dtype([("n_leapfrog", "<u8"), ("depth_sum", "<u8"), ("accept_stat_sum", "<f8"), ("divergent", "<u4"),
+                          ("max_depth_hits", "<u4")])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -121,9 +126,9 @@ def _probe_random_walk(rprop, p):
 class FusedKernel:
     """A transition kernel whose whole step runs inside the HIP chain kernel.
 
-    kind in {"rwmh", "mala", "hmc", "ul"}.  Calling it performs ONE iteration on the device with
+    kind in {"rwmh", "mala", "hmc", "ul", "nuts"}.  Calling it performs ONE iteration on the device with
     the reference's per-step signature: `kernel(x, ll) -> (x, ll)` for rwmh/mala (the threaded
-    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul.  Successive calls use
+    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul/nuts.  Successive calls use
     successive iteration indices of the kernel's own Philox stream.
     """
 
@@ -141,10 +146,16 @@ class FusedKernel:
     def _vec(self, name):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(self.params[name], dtype=np.float64), (self.model.p,)))
 
-    def launch(self, opts: RunOpts, state_ptr, lp_ptr, out_ptr, acc_ptr):
+    def launch(self, opts: RunOpts, state_ptr, lp_ptr, out_ptr, acc_ptr, counters_ptr=None, depth_ptr=None):
+        """One lr_run_<kind> call.  NUTS has no accept counts and no threaded log-density: it takes the per-chain counters
+        (lr_nuts_counters) and the optional tree depths of the kept rows instead."""
         L = self.model._L
         h = self.model.handle
-        if self.kind == "rwmh":
+        if self.kind == "nuts":
+            v = self._vec("dmm")
+            check(_lib.bind_nuts(L).lr_run_nuts(h, state_ptr, float(self.params["eps"]), int(self.params["max_depth"]), v.ctypes.data,
+                                                C.byref(opts), out_ptr, counters_ptr, depth_ptr))
+        elif self.kind == "rwmh":
             v = self._vec("prop_sd")
             check(L.lr_run_rwmh(h, state_ptr, lp_ptr, v.ctypes.data, C.byref(opts), out_ptr, acc_ptr))
         elif self.kind == "mala":
@@ -275,6 +286,85 @@ def hmcKernel(lpi, glpi, eps=1e-4, l=10, dmm=1):
     return kern
 
 
+def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10):
+    """The No-U-Turn sampler with diagonal metric, in the reference HMC's convention (fit-np-hmc.py:65-87): p ~ N(0, dmm),
+    H = -lpi(q) + sum(p^2 / dmm) / 2, q += eps * p / dmm.  Multinomial NUTS, iterative with U-turn checkpoints, at most `max_depth`
+    doublings (DESIGN.md "NUTS").  `blackjax.nuts(lpost, eps, pre)` (fit-blackjax-nuts.py:101) is `nutsKernel(lpost, glp, eps, 1 / pre)`.
+
+    A LogReg's closures give a FusedKernel (include/logreg_hip_nuts.h); any other callables a plain NumPy NUTS that draws from
+    NumPy's global generator, like the other generic kernels."""
+    max_depth = int(max_depth)
+    if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
+        raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
+    model = _model_of(lpi, "lpost")
+    if model is not None and _model_of(glpi, "glp") is model:
+        return FusedKernel("nuts", model, eps=float(eps), dmm=dmm, max_depth=max_depth)
+    return _numpy_nuts(lpi, glpi, float(eps), dmm, max_depth)
+
+
+def _numpy_nuts(lpi, glpi, eps, dmm, max_depth):
+    """The same algorithm on NumPy arrays for arbitrary callables (the generic path: NumPy's global generator, no model arithmetic of
+    its own)."""
+    def turning(c, a, b, rho):
+        r = rho - 0.5 * (a + b)
+        return np.dot(c * a, r) <= 0 or np.dot(c * b, r) <= 0
+
+    def lae(a, b):
+        return np.logaddexp(a, b)
+
+    def kern(q):
+        q = np.asarray(q, dtype=np.float64)
+        dm = np.broadcast_to(np.asarray(dmm, dtype=np.float64), q.shape)
+        c = 1.0 / dm
+        x, g, lp = q, np.asarray(glpi(q), dtype=np.float64), float(lpi(q))
+        p0 = np.random.randn(len(q)) * np.sqrt(dm)
+        H0 = 0.5 * np.sum(c * p0 * p0) - lp
+        ends = {-1: (x, p0, g), 1: (x, p0, g)}
+        rho, W, prop = p0.copy(), 0.0, x
+        for d in range(max_depth):
+            sgn = 1 if np.random.rand() < 0.5 else -1
+            cq, cp, cg = ends[sgn]
+            pinner, rhos, Ws, ck, stop = cp, np.zeros_like(q), 0.0, {}, False
+            sub = pfirst = None
+            for i in range(2 ** d):
+                cp = cp + sgn * 0.5 * eps * cg
+                cq = cq + sgn * eps * c * cp
+                lpl, cg = float(lpi(cq)), np.asarray(glpi(cq), dtype=np.float64)
+                cp = cp + sgn * 0.5 * eps * cg
+                delta = 0.5 * np.sum(c * cp * cp) - lpl - H0
+                if not np.isfinite(delta) or delta > 1000:
+                    return prop  # divergence: the subtree is discarded, the iteration ends
+                rhos = rhos + cp
+                if i == 0:
+                    Ws, sub, pfirst = -delta, cq, cp
+                else:
+                    Wn = lae(Ws, -delta)
+                    if np.random.rand() < np.exp(-delta - Wn):
+                        sub = cq
+                    Ws = Wn
+                imax = bin(i >> 1).count("1")
+                if i % 2 == 0:
+                    ck[imax] = (cp, rhos)
+                else:
+                    imin = imax - (len(bin(i)) - len(bin(i).rstrip("1"))) + 1
+                    if any(turning(c, ck[j][0], cp, rhos - ck[j][1] + ck[j][0]) for j in range(imin, imax + 1)):
+                        stop = True
+                        break
+            if stop:
+                return prop
+            if np.random.rand() < np.exp(Ws - W):
+                prop = sub
+            W = lae(W, Ws)
+            pouter = ends[-sgn][1]
+            ends[sgn] = (cq, cp, cg)
+            rho_old, rho = rho, rho + rhos
+            if (turning(c, ends[-1][1], ends[1][1], rho) or turning(c, pouter, pfirst, rho_old + pfirst)
+                    or turning(c, cp, pinner, rhos + pinner)):
+                return prop
+        return prop
+    return kern
+
+
 # ------------------------------------------------------------------------------------------------
 class ChainSet:
     """C chains of one FusedKernel, resident on the device between launches.
@@ -311,6 +401,10 @@ class ChainSet:
         self.lp = DeviceArray.from_host(m.device, lp0, dtype=np.float64)
         self.acc = DeviceArray(m.device, (self.C,), np.uint32)
         self.acc.zero_()
+        self.counters = None  # NUTS: per-chain lr_nuts_counters, added to by every launch
+        if kernel.kind == "nuts":
+            self.counters = DeviceArray(m.device, (self.C,), NUTS_COUNTERS)
+            self.counters.zero_()
         check(m._L.lr_stream_sync(m.device, None))
         # streaming statistics (enable_stats): device buffer [slots, C, 2, p], batch length, kept samples folded in
         self.stats = None
@@ -343,10 +437,13 @@ class ChainSet:
         if pivot is not None:
             self.pivot = np.asarray(pivot, dtype=np.float64).copy()
 
-    def advance(self, iters: int, thin: int, keep: bool = True, out: DeviceArray | None = None, stats: bool | None = None):
+    def advance(self, iters: int, thin: int, keep: bool = True, out: DeviceArray | None = None, stats: bool | None = None,
+                depth: DeviceArray | None = None):
         """One fused launch: iters*thin iterations per chain.  keep: return the thinned samples `[iters, C, p]`
         (a DeviceArray); stats (default: on when enable_stats was called): fold the kept samples into the
-        streaming statistics -- with keep=False nothing of size iters*C*p is ever allocated."""
+        streaming statistics -- with keep=False nothing of size iters*C*p is ever allocated.
+        depth (NUTS): an int8 DeviceArray `[iters, C]` that receives the tree depth of the iteration behind each kept row (negated
+        when it diverged)."""
         m = self.model
         if keep and out is None:
             out = DeviceArray(m.device, (iters, self.C, m.p), m.np_dtype)
@@ -359,7 +456,10 @@ class ChainSet:
                 raise ValueError("advance(stats=True) needs enable_stats(batch, slots) first")
             opts.stats, opts.stats_batch = self.stats.ptr, self.stats_batch
             opts.stats_first, opts.stats_slots = self.stats_kept, self.stats.shape[0]
-        self.kernel.launch(opts, self.state.ptr, self.lp.ptr, out.ptr if keep else None, self.acc.ptr)
+        if depth is not None and (self.kernel.kind != "nuts" or depth.shape != (int(iters), self.C) or depth.dtype != np.int8):
+            raise ValueError(f"depth= takes an int8 [iters, C] = [{int(iters)}, {self.C}] array of a NUTS chain set")
+        self.kernel.launch(opts, self.state.ptr, self.lp.ptr, out.ptr if keep else None, self.acc.ptr,
+                           self.counters.ptr if self.counters is not None else None, depth.ptr if depth is not None else None)
         self.iter_offset += int(iters) * int(thin)
         if use_stats:
             self.stats_kept += int(iters)
@@ -397,6 +497,22 @@ class ChainSet:
         self.sync()
         return self.acc.to_host()
 
+    def get_counters(self) -> np.ndarray:
+        """NUTS: the per-chain counters `[C]` (fields of lr_nuts_counters: n_leapfrog, depth_sum, accept_stat_sum, divergent,
+        max_depth_hits), summed over every launch of this chain set."""
+        if self.counters is None:
+            raise ValueError("counters exist for NUTS chain sets only")
+        self.sync()
+        return self.counters.to_host()
+
+    def nuts_info(self) -> dict:
+        """NUTS: per-chain n_leapfrog, divergent, max_depth_hits, mean_depth and mean_accept_stat over the iterations run so far."""
+        c = self.get_counters()
+        n = max(self.iter_offset, 1)
+        return {"n_leapfrog": c["n_leapfrog"].astype(np.int64), "divergent": c["divergent"].astype(np.int64),
+                "max_depth_hits": c["max_depth_hits"].astype(np.int64), "mean_depth": c["depth_sum"] / n,
+                "mean_accept_stat": c["accept_stat_sum"] / n}
+
     # -- checkpoint / resume (the reference has none: a run is all-or-nothing).  Because the random
     # stream is counter-based, (state, threaded ll, iteration counter, seed, chain offset) IS the
     # complete sampler state: a resumed run continues bit-for-bit.
@@ -415,6 +531,9 @@ class ChainSet:
               "iter_offset": np.int64(self.iter_offset), "seed": np.uint64(self.seed),
               "chain_offset": np.int64(self.chain_offset), "plan_chains": np.int64(self.plan_chains),
               "plan_first": np.int64(self.plan_first), **self._fingerprint()}
+        if self.counters is not None:  # NUTS counters, field by field
+            cn = self.counters.to_host()
+            ck.update({"nuts_" + f: cn[f].copy() for f in NUTS_COUNTERS.names})
         if self.stats is not None:  # the statistics window travels with the run
             ck.update(stats=self.stats.to_host(), stats_batch=np.int64(self.stats_batch), stats_kept=np.int64(self.stats_kept),
                       stats_pivot=np.asarray(self.pivot, dtype=np.float64))
@@ -455,6 +574,11 @@ class ChainSet:
                                  f"{val!r} here (a resumed run would silently stop being the continuation)")
         cs.iter_offset = int(ckpt["iter_offset"])
         cs.acc.copy_from(np.asarray(ckpt["accepts"], dtype=np.uint32))
+        if cs.counters is not None and "nuts_n_leapfrog" in ckpt:
+            cn = np.zeros(cs.C, dtype=NUTS_COUNTERS)
+            for f in NUTS_COUNTERS.names:
+                cn[f] = ckpt["nuts_" + f]
+            cs.counters.copy_from(cn)
         if "stats" in ckpt:
             st = np.asarray(ckpt["stats"], dtype=np.float64)
             cs.enable_stats(int(ckpt["stats_batch"]), st.shape[0], pivot=ckpt["stats_pivot"])
@@ -463,12 +587,17 @@ class ChainSet:
         return cs
 
 
-def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int) -> int:
+def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_iter: float | None = None) -> int:
     """Kept samples per launch.  A launch is bounded to ~2e9 data-element visits per chain (a few
     hundred ms at Pima scale): short enough to report progress and to stay far from any watchdog,
-    long enough that launch overhead is invisible.  Chunking never changes the samples."""
-    evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1}[kernel.kind]
-    work_per_kept = max(1, thin * evals * kernel.model.n * kernel.model.p)
+    long enough that launch overhead is invisible.  Chunking never changes the samples.
+    NUTS: `evals_per_iter` (leapfrog steps per iteration seen so far, the widest chain's) or, before any, the full tree's
+    2^max_depth - 1."""
+    if kernel.kind == "nuts":
+        evals = evals_per_iter if evals_per_iter else 2 ** int(kernel.params["max_depth"]) - 1
+    else:
+        evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1}[kernel.kind]
+    work_per_kept = max(1, int(thin * evals * kernel.model.n * kernel.model.p))
     return int(max(1, min(iters, 2_000_000_000 // work_per_kept)))
 
 
@@ -509,8 +638,15 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     cs = ChainSet(kernel, init, seed, chain_offset=chain_offset, ll=ll, group=group, mode=mode, precision=precision,
                   plan_chains=plan_chains, plan_first=plan_first)
     m = kernel.model
+    nuts = kernel.kind == "nuts"
+    auto = chunk is None
     if chunk is None:
         chunk = _auto_chunk(kernel, cs.C, thin, iters)
+
+    def rechunk():  # NUTS: from the counters of the chunks so far (the widest chain bounds a lockstep launch)
+        if nuts and auto and cs.iter_offset > 0:
+            return _auto_chunk(kernel, cs.C, thin, iters, float(cs.get_counters()["n_leapfrog"].max()) / cs.iter_offset)
+        return chunk
     if summary_only:
         from .diagnostics import choose_batches
         batch, slots = choose_batches(iters, max_batches)
@@ -523,13 +659,18 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             cs.advance(k, thin, keep=False)
             cs.sync()
             done += k
+            chunk = rechunk()
             if verb:
                 print(str(done), end=" ", flush=True)
         if verb:
             print("\nDone.", flush=True)
         res = cs.stats_summary()
-        res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)), batch=batch, seed=seed,
-                   plan=cs.plan(), state=cs.get_state())
+        if nuts:  # the mean acceptance statistic in place of an acceptance rate
+            ni = cs.nuts_info()
+            res.update(ni, accept_rate=float(np.mean(ni["mean_accept_stat"])))
+        else:
+            res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)))
+        res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
         return res
     mat = np.empty((iters, cs.C, m.p), dtype=m.np_dtype)
     if verb:
@@ -542,14 +683,18 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         mat[done:done + k] = out.to_host()
         out.free()
         done += k
+        chunk = rechunk()
         if verb:
             print(str(done), end=" ", flush=True)
     if verb:
         print("\nDone.", flush=True)
     res = mat[:, 0, :].astype(np.float64) if single else mat
     if return_info:
-        info = {"accepts": cs.get_accepts(), "state": cs.get_state(), "ll": cs.get_ll(), "seed": seed,
-                "plan": cs.plan(), "iterations": iters * thin}
+        if nuts:  # per chain: n_leapfrog, divergent, max_depth_hits, mean_depth, mean_accept_stat
+            info = {"state": cs.get_state(), "seed": seed, "plan": cs.plan(), "iterations": iters * thin, **cs.nuts_info()}
+        else:
+            info = {"accepts": cs.get_accepts(), "state": cs.get_state(), "ll": cs.get_ll(), "seed": seed,
+                    "plan": cs.plan(), "iterations": iters * thin}
         if getattr(kernel, "proposal", None):  # RWMH: how the proposal was recognised ("rwProposal" | "probed": mhKernel)
             info["proposal"] = kernel.proposal
         return res, info
