@@ -1,12 +1,21 @@
 """The fused NUTS kernel (logreg_amd/csrc/lr_nuts.h, include/logreg_hip_nuts.h) on the MI355X: step parity with the CPU test double of
 the same ABI, the posterior against the reference's, bit exactness of reruns / chunks / shards / the second build, the saturated
-BlackJAX setting, non-finite starts, fresh models and the planner."""
+BlackJAX setting, non-finite starts, fresh models and the planner.
+
+Against the independent reference (tests/nuts_reference.py: one transition restated without the checkpoint scheme): the float64 kernel
+transition by transition at p = 3 .. 32 (every width class, 1 / 3 / 65 / 257 chains, trees to depth 7 and beyond) and, at the same
+inputs, against the double; the float32 kernel against the float64 reference wherever the reference's decision margin exceeds the
+measured float32 threshold; shards that start at chain ids 1, 2, 3 (mod 4) with odd lengths and mixed neighbours (non-finite, tail
+and ordinary starts) against the whole run, bytes for bytes."""
+import collections
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from conftest import load_golden
+
+import nuts_reference as nr
 
 pytestmark = pytest.mark.gpu
 
@@ -175,3 +184,125 @@ def test_planner_reports_the_nuts_variant(la, models, pima):
     tall = la.LogReg(rng.standard_normal((20000, 8)), (rng.random(20000) < 0.5).astype(float), 1.0)
     with pytest.raises(la.LogregHipError, match="beyond"):
         la.mcmc(np.zeros(8), la.nutsKernel(tall.lpost, tall.glp), iters=1, verb=False)
+
+
+@pytest.fixture(scope="module")
+def kernel_vs_reference(la):
+    """nr.GPU_F64_CASES on the float64 kernel, the reference and the double, the last two from the kernel's own inputs"""
+    import twin_nuts
+    from oracle.oracle import OracleModel
+    res = []
+    for case in nr.GPU_F64_CASES:
+        X, y, ps = nr.synthetic_model(case.p, case.n, 100 + case.p)
+        dmm, q0 = nr.case_metric_and_start(case)
+        steps = nr.run_stepwise(la, la.LogReg(X, y, ps, dtype="float64"), q0, case.K, case.eps, dmm, case.max_depth, case.seed,
+                                case.chain_offset, case.iter_offset)
+        om = OracleModel(X, y, ps)
+        refs = nr.reference_steps(om.lpost, om.glp, steps, case.eps, dmm, case.max_depth, case.seed, case.chain_offset, case.iter_offset)
+        res.append([case, steps, refs, None])
+    twin_nuts.install()
+    try:
+        for r in res:
+            case = r[0]
+            X, y, ps = nr.synthetic_model(case.p, case.n, 100 + case.p)
+            dmm, q0 = nr.case_metric_and_start(case)
+            r[3] = nr.run_stepwise(la, la.LogReg(X, y, ps, dtype="float64"), q0, case.K, case.eps, dmm, case.max_depth, case.seed,
+                                   case.chain_offset, case.iter_offset, forced=r[1])
+    finally:
+        twin_nuts.uninstall()
+    return res
+
+
+def test_float64_kernel_equals_the_reference_at_every_width(kernel_vs_reference):
+    """Teacher-forced, as tests/test_nuts_reference_cpu.py compares the double: signed depth, leaf count and flags equal, state and
+    acceptance statistic within nr.F64_TOL (10 x the deviation measured between the double and the reference on the CPU; the kernel's
+    row sums are a third summation order).  A transition is left out only below a reference margin of 1e-9, at most 1 in 1000.
+    The cases must reach depth 7 and beyond in every width class (the second leaf-uniform block, deep checkpoints with two
+    coordinates per lane) and every stop reason but 'check 2 / 3 only', which the CPU module counts."""
+    n = skipped = 0
+    worst, mism = 0.0, []
+    cnt, deep = collections.Counter(), collections.Counter()
+    for case, steps, refs, _ in kernel_vs_reference:
+        cn, cs, cm, cw = nr.compare(steps, refs, nr.MIN_MARGIN)
+        n, skipped, worst = n + cn, skipped + cs, max(worst, cw)
+        mism += [f"{case}: {m}" for m in cm]
+        P = 4 if case.p <= 4 else 8 if case.p <= 8 else 16 if case.p <= 16 else 32
+        for row in refs:
+            for r in row:
+                cnt[r.reason] += 1
+                deep[P] += abs(r.depth) >= 7
+    print(f"kernel vs reference: {n} transitions, {skipped} skipped, largest relative deviation {worst:.3g};", dict(cnt),
+          "depth >= 7 per padded width:", dict(deep))
+    assert not mism, "\n".join(mism[:20])
+    assert skipped <= n / 1000
+    assert worst <= nr.F64_TOL
+    assert all(deep[P] >= 10 for P in (4, 8, 16, 32)), dict(deep)
+    for reason in (nr.DIVERGENCE, nr.SUBTREE, nr.TREE):
+        assert cnt[reason] >= 20, dict(cnt)
+    assert {c.p for c, _, _, _ in kernel_vs_reference} == {3, 4, 5, 8, 9, 16, 17, 31, 32}
+    assert {c.C for c, _, _, _ in kernel_vs_reference} == {1, 3, 65, 257}
+
+
+def test_float64_kernel_equals_the_double_at_every_width(kernel_vs_reference):
+    """test_step_parity_with_the_test_double's assertions at the other widths, from the same inputs: depths and counters equal, states
+    to 1e-7 relative."""
+    for case, steps, _, twin in kernel_vs_reference:
+        for k, (g, t) in enumerate(zip(steps, twin)):
+            for f in ("depth", "n_leapfrog", "divergent", "max_depth_hits"):
+                assert np.array_equal(g[f], t[f]), (case, k, f, np.argwhere(g[f] != t[f])[:10].tolist())
+            np.testing.assert_allclose(g["x_out"], t["x_out"], rtol=1e-7, atol=1e-12, err_msg=str((case, k)))
+            np.testing.assert_allclose(g["accept_stat_sum"], t["accept_stat_sum"], rtol=1e-7, err_msg=str((case, k)))
+
+
+def test_float32_kernel_equals_the_float64_reference_beyond_the_margin(la):
+    """The float32 kernel teacher-forced against the float64 reference on the float32-rounded data and state.  Where the reference's
+    margin exceeds nr.F32_TAU the signed depth, leaf count and flags are equal and the state and acceptance statistic agree to
+    nr.F32_STATE_TOL.  Neither number comes from the kernel: they are 8 x what the reference's NumPy-float32 mode showed against its
+    float64 mode on the CPU (tests/test_nuts_reference_cpu.py, profiles/r8_nuts_reference.txt); the kernel's summation order is a third
+    one with an error of that size.  At most 10 % of the transitions fall below the margin."""
+    from oracle.oracle import OracleModel
+    n = skipped = 0
+    worst, mism = 0.0, []
+    for case in nr.F32_CASES:
+        X, y, ps, dmm, q0 = nr.float32_problem(case)
+        steps = nr.run_stepwise(la, la.LogReg(X, y, ps, dtype="float32"), q0, case.K, case.eps, dmm, case.max_depth, case.seed,
+                                case.chain_offset, case.iter_offset)
+        assert steps[0]["x_out"].dtype == np.float32
+        om = OracleModel(X, y, ps)
+        refs = nr.reference_steps(om.lpost, om.glp, steps, case.eps, dmm, case.max_depth, case.seed, case.chain_offset, case.iter_offset)
+        cn, cs, cm, cw = nr.compare(steps, refs, nr.F32_TAU)
+        n, skipped, worst = n + cn, skipped + cs, max(worst, cw)
+        mism += [f"{case}: {m}" for m in cm]
+    print(f"float32 kernel vs float64 reference: {n} transitions, {skipped} below the margin {nr.F32_TAU:g}, largest relative deviation {worst:.3g}")
+    assert not mism, "\n".join(mism[:20])
+    assert skipped <= 0.10 * n
+    assert worst <= nr.F32_STATE_TOL
+
+
+def test_shifted_shards_with_mixed_neighbours_are_bit_exact(la, models, map_beta):
+    """A chain's result depends neither on the three chains that share its wave nor on its row in the wave.  The planned run of
+    test_bit_exact_rerun_chunks_shards_and_second_build with the chains mixed inside every wave -- non-finite starts (they finish at
+    leaf 0), starts far in the tail, ordinary ones -- and shards whose first chain is 1, 2, 3 (mod 4) with odd lengths: every chain
+    moves to another row and gets other neighbours.  Samples, depths and counters are compared as bytes."""
+    rng = np.random.default_rng(6)
+    C = 1000
+    sd = np.array([1.73, 0.065, 0.0068, 0.018, 0.023, 0.043, 0.55, 0.022])
+    q0 = map_beta + 0.1 * np.abs(map_beta) * rng.standard_normal((C, 8))
+    kind = rng.integers(0, 3, C)  # 0 ordinary, 1 non-finite, 2 tail: mixed within the waves
+    q0[kind == 1, 3] = np.nan
+    q0[kind == 2] = map_beta + 6.0 * sd * rng.standard_normal((int((kind == 2).sum()), 8))
+    fields = ("n_leapfrog", "depth_sum", "accept_stat_sum", "divergent", "max_depth_hits")
+    for dtype in ("float32", "float64"):
+        k = kern(la, models[dtype], max_depth=8)
+        full, dfull, cs = run(la, k, q0, 12, thin=2)
+        cfull = cs.get_counters()
+        assert np.all(dfull[:, kind == 1] == -1) and np.all(np.abs(dfull[:, kind != 1]) >= 1)
+        assert len({tuple(kind[w:w + 4]) for w in range(0, C, 4)}) > 20  # the waves really are mixed
+        for lo, hi in ((1, 78), (301, 432), (502, 757), (663, 1000), (998, 999)):
+            assert lo % 4 in (1, 2, 3) and (hi - lo) % 2 == 1
+            sh, dsh, css = run(la, k, q0[lo:hi], 12, thin=2, chain_offset=lo, plan_chains=C, plan_first=0)
+            assert sh.tobytes() == full[:, lo:hi].tobytes(), (dtype, lo, hi)
+            assert dsh.tobytes() == dfull[:, lo:hi].tobytes(), (dtype, lo, hi)
+            csh = css.get_counters()
+            for f in fields:
+                assert np.asarray(csh[f]).tobytes() == np.ascontiguousarray(cfull[f][lo:hi]).tobytes(), (dtype, lo, hi, f)

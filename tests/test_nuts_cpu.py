@@ -1,6 +1,8 @@
 """NUTS above the kernel, in the GPU-less container: the ABI's symbol tables, the CPU test double of include/logreg_hip_nuts.h
 (tests/host/lr_cpu_twin_nuts.c, injected by tests/twin_nuts.py for this module) against the reference's posterior, the Python face
-(nutsKernel, ChainSet, mcmc) on it, the generic NumPy NUTS, and the stream layout against the oracle's Philox."""
+(nutsKernel, ChainSet, mcmc) on it, the generic NumPy NUTS, and the stream layout against the oracle's Philox.
+The tree logic itself -- the double and the generic NumPy NUTS, transition by transition against an independent reference at every
+width, depth and stop reason -- is tests/test_nuts_reference_cpu.py."""
 import ctypes
 import os
 import re
