@@ -19,9 +19,10 @@ from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKern
                       ulKernel)
 from .model import DeviceArray, LogReg  # noqa: F401
 from .optimize import find_map, overdispersed_init  # noqa: F401
+from .predict import PosteriorPredictive, merge_predictive, predict_proba, waic, waic_from_table  # noqa: F401
 from .output import print_summary, read_parquet, to_frame, write_parquet  # noqa: F401
 
 __all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "malaKernel", "hmcKernel", "ulKernel", "nutsKernel",
            "rwProposal", "mcmc", "load_pima", "load_pima_parquet", "synthetic_logreg", "summarise", "describe",
            "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "overdispersed_init", "write_parquet",
-           "read_parquet", "to_frame", "print_summary"]
+           "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table"]

@@ -95,8 +95,20 @@ NUTS_SYMBOLS = {
     "lr_run_nuts": (C.c_int, [_vp, _vp, C.c_double, _i32, _vp, _op, _vp, _vp, _vp]),
 }
 
+PRED_ROWS = 5  # LR_PRED_ROWS
+# name -> (restype, argtypes); every symbol include/logreg_hip_predict.h declares.  A table of its own like NUTS_SYMBOLS, bound on
+# first use (load_predict): the test doubles bind SYMBOLS / NUTS_SYMBOLS onto libraries that do not have these
+PREDICT_SYMBOLS = {
+    "lr_predict_create": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_vp)]),
+    "lr_predict_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_predict_result": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "lr_predict_reset": (C.c_int, [_vp]),
+    "lr_predict_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
+_predict = None
 
 
 def bind_nuts(L):
@@ -115,6 +127,24 @@ def bind_nuts(L):
 def load_nuts():
     """The library with the NUTS entry points bound (the same liblogreg_hip.so as load())."""
     return bind_nuts(load())
+
+
+def bind_predict(L):
+    """`L` (a loaded library handle) with the prediction entry points bound; resolved once per handle."""
+    global _predict
+    if _predict is L:
+        return L
+    for name, (res, args) in PREDICT_SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+        fn.restype = res
+        fn.argtypes = args
+    _predict = L
+    return L
+
+
+def load_predict():
+    """The library with the prediction entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_predict(load())
 
 
 def load():

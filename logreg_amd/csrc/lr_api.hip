@@ -5,10 +5,12 @@
 // All arithmetic of the path runs in the kernels (lr_kernels.h, lr_mfma.h, lr_tall*.h, lr_wide*.h).
 #include "../../include/logreg_hip.h"
 #include "../../include/logreg_hip_nuts.h"
+#include "../../include/logreg_hip_predict.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -21,6 +23,7 @@
 #include "lr_nuts.h"
 #include "lr_hessian.h"
 #include "lr_mfma.h"
+#include "lr_predict.h"
 #include "lr_stats.h"
 #include "lr_tall.h"
 #include "lr_tall_mx.h"
@@ -239,8 +242,10 @@ int lr_model_create(const double* X, const double* y, int64_t n, int32_t p, cons
     // signed rows  xs_i = (2 y_i - 1) x_i, zero-padded to P columns, in the compute dtype
     const size_t elems = (size_t)n * m->P;
     std::vector<unsigned char> host(elems * m->esize());
+    m->ysign.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const double s = 2.0 * y[i] - 1.0;
+        m->ysign[(size_t)i] = (signed char)s;
         for (int j = 0; j < m->P; ++j) {
             const double v = j < p ? s * X[i * p + j] : 0.0;
             if (!std::isfinite(v)) { delete m; return fail(LR_ERR_INVALID, "X[%lld,%d] is not finite", (long long)i, j); }
@@ -662,6 +667,217 @@ int lr_stats_reduce(int device, const double* stats, int64_t n_chains, int32_t p
     LR_HIP(hipMemcpyAsync(sums, d_sums, (size_t)lr::kStatsRows * p * sizeof(double), hipMemcpyDeviceToHost, st));
     LR_HIP(hipStreamSynchronize(st));
     return LR_OK;
+}
+
+// ---- posterior prediction, pointwise log-likelihood (include/logreg_hip_predict.h; kernels: lr_predict.h) ----------------------------
+}  // extern "C"
+struct lr_predict {
+    lr_model* m = nullptr;
+    int device = 0;                 // the model's (kept here: lr_predict_destroy must not need the model)
+    int64_t r = 0;
+    bool labels = false;
+    void* d_rows = nullptr;         // [r][P] signed rows in the model's dtype (the model's own d_rows when own_rows is false)
+    bool own_rows = false;
+    signed char* d_sign = nullptr;  // [r] 2 y - 1 (labels only)
+    double* d_acc = nullptr;        // [LR_PRED_ROWS][r] the running table
+    int64_t n = 0;                  // draws folded in
+    hipStream_t last = nullptr;     // stream of the last accumulate call
+    // grow-only workspaces: slice partials, host draws staged on the device, draws padded to the kernel width
+    void* d_part = nullptr;  size_t part_bytes = 0;
+    void* d_in = nullptr;    size_t in_bytes = 0;
+    void* d_pad = nullptr;   size_t pad_bytes = 0;
+};
+namespace {
+static_assert(LR_PRED_ROWS == lr::kPredRows, "table rows");
+
+int pred_grow(void** p, size_t* have, size_t want, const char* what) {
+    if (*have >= want) return LR_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_predict: allocating %zu bytes of %s failed", want, what);
+    *have = want;
+    return LR_OK;
+}
+
+// slices of one launch over S draws: enough workgroups for four waves on every SIMD, at least 64 draws each
+int64_t pred_most_slices(const lr_predict* pp, int64_t S) {  // non-decreasing in S
+    const int64_t tiles = (pp->r + lr::kPredBlock - 1) / lr::kPredBlock;
+    const int64_t want_blocks = (int64_t)(pp->m->cus > 0 ? pp->m->cus : 256) * 4;
+    int64_t sl = (want_blocks + tiles - 1) / tiles;
+    const int64_t most = (S + 63) / 64;
+    if (sl > most) sl = most;
+    return sl < 1 ? 1 : sl;
+}
+void pred_slicing(const lr_predict* pp, int64_t S, int64_t* per, int64_t* slices) {
+    const int64_t sl = pred_most_slices(pp, S);
+    *per = (S + sl - 1) / sl;
+    *slices = (S + *per - 1) / *per;  // every slice non-empty
+}
+
+template <typename T, int P>
+int pred_launch(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) {
+    int64_t per, slices;
+    pred_slicing(pp, S, &per, &slices);
+    const int64_t tiles = (pp->r + lr::kPredBlock - 1) / lr::kPredBlock;
+    const size_t want = (size_t)slices * lr::kPredRows * pp->r * sizeof(double);
+    if (const int rc = pred_grow(&pp->d_part, &pp->part_bytes, want, "slice partials")) return rc;
+    const dim3 grid((unsigned)tiles, (unsigned)slices);
+    if (pp->labels)
+        hipLaunchKernelGGL((lr::k_predict_partial<T, P, true>), grid, dim3(lr::kPredBlock), 0, st, static_cast<const T*>(pp->d_rows), pp->d_sign, pp->r,
+                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->d_part));
+    else
+        hipLaunchKernelGGL((lr::k_predict_partial<T, P, false>), grid, dim3(lr::kPredBlock), 0, st, static_cast<const T*>(pp->d_rows), pp->d_sign, pp->r,
+                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->d_part));
+    LR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lr::k_predict_merge, dim3((unsigned)((pp->r + lr::kPredMergeRows - 1) / lr::kPredMergeRows)),
+                       dim3(lr::kPredMergeRows, lr::kPredMergeWays), 0, st, static_cast<const double*>(pp->d_part), slices, per, S, pp->r, (double)pp->n,
+                       pp->d_acc);
+    LR_HIP(hipGetLastError());
+    pp->n += S;
+    return LR_OK;
+}
+int pred_launch_any(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) {
+    const lr_model* m = pp->m;
+    switch (m->P) {  // every padded width the library has, both dtypes
+#define LR_PRED_CASE(W) \
+    case W: return m->dtype == LR_F32 ? pred_launch<float, W>(pp, d_draws, S, st) : pred_launch<double, W>(pp, d_draws, S, st);
+        LR_PRED_CASE(4) LR_PRED_CASE(8) LR_PRED_CASE(16) LR_PRED_CASE(32) LR_PRED_CASE(64) LR_PRED_CASE(128)
+#undef LR_PRED_CASE
+    }
+    return fail(LR_ERR_UNSUPPORTED, "lr_predict: unsupported padded width %d", m->P);
+}
+}  // namespace
+extern "C" {
+
+int lr_predict_create(lr_model* m, const double* X_new, const double* y_new, int64_t r, lr_predict** out) {
+    if (!m || !out) return fail(LR_ERR_INVALID, "lr_predict_create: model / out is NULL");
+    if (r <= 0) return fail(LR_ERR_INVALID, "lr_predict_create: r must be positive (got %lld)", (long long)r);
+    if (r > 0x7FFFFFFFll * lr::kPredMergeRows) return fail(LR_ERR_UNSUPPORTED, "lr_predict_create: r = %lld is beyond the launch grid", (long long)r);
+    if (!X_new && y_new) return fail(LR_ERR_INVALID, "lr_predict_create: y_new without X_new (X_new = NULL means the model's own design AND labels)");
+    if (!X_new && r != m->n) return fail(LR_ERR_INVALID, "lr_predict_create: X_new = NULL means the model's own %lld rows, r = %lld", (long long)m->n, (long long)r);
+    if (y_new)
+        for (int64_t i = 0; i < r; ++i)
+            if (y_new[i] != 0.0 && y_new[i] != 1.0) return fail(LR_ERR_INVALID, "lr_predict_create: y_new[%lld]=%g is not 0/1", (long long)i, y_new[i]);
+    LR_HIP(hipSetDevice(m->device));
+    hipError_t e;
+    lr_predict* pp = new lr_predict();
+    pp->m = m;
+    pp->device = m->device;
+    pp->r = r;
+    pp->labels = !X_new || y_new;
+    std::vector<signed char> sg;
+    if (X_new) {
+        const int p = m->p, P = m->P;
+        std::vector<unsigned char> host((size_t)r * P * m->esize());
+        if (y_new) sg.resize((size_t)r);
+        for (int64_t i = 0; i < r; ++i) {
+            const double s = y_new ? 2.0 * y_new[i] - 1.0 : 1.0;
+            if (y_new) sg[(size_t)i] = (signed char)s;
+            for (int j = 0; j < P; ++j) {
+                const double v = j < p ? s * X_new[i * p + j] : 0.0;
+                if (!std::isfinite(v)) { delete pp; return fail(LR_ERR_INVALID, "lr_predict_create: X_new[%lld,%d] is not finite", (long long)i, j); }
+                if (m->dtype == LR_F32) reinterpret_cast<float*>(host.data())[i * P + j] = (float)v;
+                else reinterpret_cast<double*>(host.data())[i * P + j] = v;
+            }
+        }
+        pp->own_rows = true;
+        if (hipMalloc(&pp->d_rows, host.size()) != hipSuccess) {
+            lr_predict_destroy(pp);
+            return fail(LR_ERR_NOMEM, "lr_predict_create: allocating %zu bytes of rows failed", host.size());
+        }
+        if ((e = hipMemcpy(pp->d_rows, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+            lr_predict_destroy(pp);
+            return fail(LR_ERR_HIP, "lr_predict_create: copying the rows failed: %s", hipGetErrorString(e));
+        }
+    } else {
+        pp->d_rows = m->d_rows;
+    }
+    const std::vector<signed char>& signs = X_new ? sg : m->ysign;
+    if (pp->labels && hipMalloc((void**)&pp->d_sign, (size_t)r) != hipSuccess) {
+        lr_predict_destroy(pp);
+        return fail(LR_ERR_NOMEM, "lr_predict_create: allocating the labels failed");
+    }
+    if (pp->labels && (e = hipMemcpy(pp->d_sign, signs.data(), (size_t)r, hipMemcpyHostToDevice)) != hipSuccess) {
+        lr_predict_destroy(pp);
+        return fail(LR_ERR_HIP, "lr_predict_create: copying the labels failed: %s", hipGetErrorString(e));
+    }
+    if (hipMalloc((void**)&pp->d_acc, (size_t)LR_PRED_ROWS * r * sizeof(double)) != hipSuccess) {
+        lr_predict_destroy(pp);
+        return fail(LR_ERR_NOMEM, "lr_predict_create: allocating the table failed");
+    }
+    *out = pp;
+    return LR_OK;
+}
+
+int lr_predict_accumulate(lr_predict* pp, const void* draws, int64_t S, int32_t on_device, void* stream) {
+    if (!pp || !draws) return fail(LR_ERR_INVALID, "lr_predict_accumulate: accumulator / draws is NULL");
+    if (S <= 0) return fail(LR_ERR_INVALID, "lr_predict_accumulate: S must be positive (got %lld)", (long long)S);
+    lr_model* m = pp->m;
+    LR_HIP(hipSetDevice(pp->device));
+    hipStream_t st = (hipStream_t)stream;
+    pp->last = st;
+    const size_t es = m->esize(), in_row = (size_t)m->p * es, k_row = (size_t)m->P * es;
+    const bool pad = m->p != m->P;
+    // pieces of at most 256 MB of kernel-width draws: bounds the staging buffers; the grid's y extent stays far below its limit
+    const int64_t piece = std::max<int64_t>(1024, (int64_t)((size_t(256) << 20) / k_row));
+    // every workspace at the size of the largest (the first) piece before anything is folded in: running out of memory leaves the
+    // accumulator as it was
+    const int64_t S0 = std::min(piece, S);
+    if (!on_device)
+        if (const int rc = pred_grow(&pp->d_in, &pp->in_bytes, (size_t)S0 * in_row, "staged draws")) return rc;
+    if (pad)
+        if (const int rc = pred_grow(&pp->d_pad, &pp->pad_bytes, (size_t)S0 * k_row, "padded draws")) return rc;
+    if (const int rc = pred_grow(&pp->d_part, &pp->part_bytes, (size_t)pred_most_slices(pp, S0) * lr::kPredRows * pp->r * sizeof(double), "slice partials"))
+        return rc;
+    for (int64_t s0 = 0; s0 < S; s0 += piece) {
+        const int64_t Sb = std::min(piece, S - s0);
+        const void* src = static_cast<const unsigned char*>(draws) + (size_t)s0 * in_row;
+        if (!on_device) {
+            LR_HIP(hipMemcpyAsync(pp->d_in, src, (size_t)Sb * in_row, hipMemcpyHostToDevice, st));
+            src = pp->d_in;
+        }
+        if (pad) {
+            const unsigned blocks = (unsigned)(((size_t)Sb * m->P + 255) / 256);
+            if (m->dtype == LR_F32)
+                hipLaunchKernelGGL(lr::k_predict_pad<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(src), Sb, m->p, m->P, static_cast<float*>(pp->d_pad));
+            else
+                hipLaunchKernelGGL(lr::k_predict_pad<double>, dim3(blocks), dim3(256), 0, st, static_cast<const double*>(src), Sb, m->p, m->P, static_cast<double*>(pp->d_pad));
+            LR_HIP(hipGetLastError());
+            src = pp->d_pad;
+        }
+        if (const int rc = pred_launch_any(pp, src, Sb, st)) return rc;
+    }
+    if (!on_device) LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_predict_result(lr_predict* pp, double* table, int64_t* n_draws) {
+    if (!pp || !table) return fail(LR_ERR_INVALID, "lr_predict_result: accumulator / table is NULL");
+    LR_HIP(hipSetDevice(pp->device));
+    const size_t cells = (size_t)LR_PRED_ROWS * pp->r;
+    if (pp->n > 0) {
+        LR_HIP(hipMemcpyAsync(table, pp->d_acc, cells * sizeof(double), hipMemcpyDeviceToHost, pp->last));
+        LR_HIP(hipStreamSynchronize(pp->last));
+    }
+    for (size_t e = pp->n > 0 ? (pp->labels ? cells : 2 * (size_t)pp->r) : 0; e < cells; ++e) table[e] = NAN;
+    if (n_draws) *n_draws = pp->n;
+    return LR_OK;
+}
+
+int lr_predict_reset(lr_predict* pp) {
+    if (!pp) return fail(LR_ERR_INVALID, "lr_predict_reset: accumulator is NULL");
+    pp->n = 0;  // the next merge starts the table afresh without reading it
+    return LR_OK;
+}
+
+void lr_predict_destroy(lr_predict* pp) {
+    if (!pp) return;
+    (void)hipSetDevice(pp->device);
+    if (pp->own_rows && pp->d_rows) (void)hipFree(pp->d_rows);
+    for (void* q : {(void*)pp->d_sign, (void*)pp->d_acc, pp->d_part, pp->d_in, pp->d_pad})
+        if (q) (void)hipFree(q);
+    delete pp;
 }
 
 // ---- device memory / stream / event helpers -------------------------------------------------------

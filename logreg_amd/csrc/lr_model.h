@@ -123,6 +123,7 @@ struct lr_model {
     int P = 0;   // padded width (4, 8, 16, 32)
     int cus = 256;
     void* d_rows = nullptr;  // [n][P] signed rows, dtype
+    std::vector<signed char> ysign;  // [n] host copy of 2 y - 1: the labels behind the signed rows (lr_predict_create with the model's own design)
     void* d_rows_tw = nullptr;  // float32, P <= 32: [ceil(n/2)][P][2] twisted row pairs (lr::ScalarRowPairs)
     double inv_var[kMaxP];
     double lprior_const = 0;

@@ -602,7 +602,8 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
 
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
-         group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0):
+         group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
+         predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -626,11 +627,18 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     model's dtype (step-for-step comparable with the float64 reference); see include/logreg_hip.h LR_PREC_*.  float64 models
     follow the same policy with more kept exact: position, momentum, end points, kinetic energies and the Metropolis test are
     float64, only the force inside the trajectory comes from float32 / 16-bit operands (4 - 6 x the all-float64 rate).
+    `predictive` (fused kernels): a `PosteriorPredictive` of the same model.  Every chunk's block of kept samples is folded into it ON
+    THE DEVICE before the block is copied or freed -- with `summary_only=True` the block lives only that long and no sample matrix reaches
+    the host; the returned dict gains `"predictive"`.  Chains, states, statistics and accept counts are those of the same call without it.
     `plan_chains`, `plan_first`: chain count to plan the kernel variant for and the global id of that run's first chain (a shard of
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
     if not isinstance(kernel, FusedKernel):
+        if predictive is not None:
+            raise ValueError("predictive= needs a fused kernel (the closures of a LogReg)")
         return _mcmc_generic(init, kernel, thin, iters, verb)
+    if predictive is not None and getattr(predictive, "model", None) is not kernel.model:
+        raise ValueError("predictive= must be a PosteriorPredictive of the kernel's own model")
     init = np.asarray(init, dtype=np.float64)
     single = init.ndim == 1
     if seed is None:
@@ -656,8 +664,14 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         done = 0
         while done < iters:
             k = min(chunk, iters - done)
-            cs.advance(k, thin, keep=False)
-            cs.sync()
+            if predictive is None:
+                cs.advance(k, thin, keep=False)
+                cs.sync()
+            else:  # the chunk's samples exist on the device just long enough to be folded into the accumulator
+                out = cs.advance(k, thin, keep=True)
+                predictive.update(out, stream=cs.stream)
+                cs.sync()
+                out.free()
             done += k
             chunk = rechunk()
             if verb:
@@ -671,6 +685,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         else:
             res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)))
         res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
+        if predictive is not None:
+            res["predictive"] = predictive
         return res
     mat = np.empty((iters, cs.C, m.p), dtype=m.np_dtype)
     if verb:
@@ -679,6 +695,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     while done < iters:
         k = min(chunk, iters - done)
         out = cs.advance(k, thin, keep=True)
+        if predictive is not None:
+            predictive.update(out, stream=cs.stream)
         cs.sync()
         mat[done:done + k] = out.to_host()
         out.free()
