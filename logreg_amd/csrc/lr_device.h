@@ -660,8 +660,17 @@ template <typename T, int P> __device__ __forceinline__ void vscale(T s, const T
 //   level 3, 4  quad_perm [2,3,0,1], [1,0,3,2] on the two remaining values                                 4 adds
 // 16 adds; every lane of quad q ends with the totals of values 2q and 2q + 1 (bit-identical in the quad's 4 lanes).
 // Inline asm: the bank-masked form (disabled lanes keep the destination) has no builtin that the DPP combiner would
-// fuse, and the compiler pads no hazards inside asm -- the leading s_nop and the instruction order below keep two
-// wait states between a VALU write of a register and its DPP read.
+// fuse, and the compiler pads no DPP hazard around or inside asm.  A DPP read of a register needs two wait states
+// (two issued instructions, or s_nop 1) after the vector write of that register:
+//   - the inputs come from the caller's v_pk_add_f32 at an unknown distance: the leading s_nop 1;
+//   - level 1 writes r0..r3 twice (one bank mask each), the second time in the order r0, r1, r2, r3 as its last four adds; level 2
+//     reads them in that same order, so three instructions lie between the last write of every r and its read;
+//   - s0, s1 (last written by the 3rd and 4th add of level 2) and u0, u1 have only ONE instruction of their own level
+//     between write and read: one s_nop 0 in front of level 3 and one in front of level 4 make the second.
+// Nothing follows the last add: the callers' next use of u0 / u1 is an ordinary (non-DPP) operand -- the prior's
+// v_pk_fma_f32, a v_cvt_f64_f32 -- for which the compiler pads what it needs itself.  A caller that read u0 or u1 through
+// DPP next would have to wait two states first.  The order of the additions is the one of the four levels above: every
+// sum has the same operands in the same association whatever the issue order.
 __device__ __forceinline__ void group16_reduce_scatter8(const float (&v)[8], float& u0, float& u1) {
     float r0, r1, r2, r3, s0, s1;
     asm volatile(
@@ -681,10 +690,9 @@ __device__ __forceinline__ void group16_reduce_scatter8(const float (&v)[8], flo
         "s_nop 0\n\t"
         "v_add_f32_dpp %6, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
         "v_add_f32_dpp %7, %5, %5 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
+        "s_nop 0\n\t"
         "v_add_f32_dpp %6, %6, %6 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %7, %7, %7 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"  // the caller's next instruction may be a DPP read of u1 (the compiler pads nothing after asm)
+        "v_add_f32_dpp %7, %7, %7 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
         : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(s0), "=&v"(s1), "=&v"(u0), "=&v"(u1)
         : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
 }
@@ -695,18 +703,19 @@ __device__ __forceinline__ float group16_quad_sum(float v) {
     v += dpp_mov<0x140>(v);  // row_mirror:      quads 0 <-> 3, 1 <-> 2
     return v;
 }
-// the reverse: every lane of a 16-lane row gets the pair held by quad q (its lane 4q) for q = 0..3: 8 v_mov_b32_dpp row_share
+// the reverse: every lane of a 16-lane row gets the pair held by quad q (its lane 4q) for q = 0..3: 4 v_mov_b64_dpp row_newbcast
+// (the 64-bit DPP move exists for row_newbcast only; it moves the (x, y) pair as one double: pure data movement)
 __device__ __forceinline__ void group16_allgather_pairs(const f32x2& mine, f32x2 (&all)[4]) {
-    const float fx = mine.x, fy = mine.y;  // (bit_cast straight from a vector-element lvalue reads element 0 for both)
-    const int mx = __builtin_bit_cast(int, fx), my = __builtin_bit_cast(int, fy);
-    all[0] = f32x2{__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, mx, 0x150, 0xF, 0xF, true)),
-                   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, my, 0x150, 0xF, 0xF, true))};
-    all[1] = f32x2{__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, mx, 0x154, 0xF, 0xF, true)),
-                   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, my, 0x154, 0xF, 0xF, true))};
-    all[2] = f32x2{__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, mx, 0x158, 0xF, 0xF, true)),
-                   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, my, 0x158, 0xF, 0xF, true))};
-    all[3] = f32x2{__builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, mx, 0x15C, 0xF, 0xF, true)),
-                   __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, my, 0x15C, 0xF, 0xF, true))};
+    const double m = __builtin_bit_cast(double, mine);
+    // (the result goes through a double temporary: a bit_cast of the call expression itself is rejected)
+    const double b0 = __builtin_amdgcn_update_dpp(0.0, m, 0x150, 0xF, 0xF, true);
+    const double b1 = __builtin_amdgcn_update_dpp(0.0, m, 0x154, 0xF, 0xF, true);
+    const double b2 = __builtin_amdgcn_update_dpp(0.0, m, 0x158, 0xF, 0xF, true);
+    const double b3 = __builtin_amdgcn_update_dpp(0.0, m, 0x15C, 0xF, 0xF, true);
+    all[0] = __builtin_bit_cast(f32x2, b0);
+    all[1] = __builtin_bit_cast(f32x2, b1);
+    all[2] = __builtin_bit_cast(f32x2, b2);
+    all[3] = __builtin_bit_cast(f32x2, b3);
 }
 
 // min(a, b) that keeps a NaN: v_minimum3_f32 (gfx950).  The clamps in front of an exponential use it -- fminf returns its OTHER operand

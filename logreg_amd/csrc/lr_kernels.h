@@ -140,9 +140,12 @@ __global__ void __launch_bounds__(256) k_eval(ModelArgs<T, P> m, EvalArgs<T> a) 
 // --------------------------------------------------------------------------------------------
 // HMC interior leapfrog loop for the 16-lanes-per-chain register kernel (float, P = 8): l - 1 x (drift, gradient,
 // kick) with the position and momentum of a chain DISTRIBUTED over its 16 lanes -- quad q owns coordinates 2q, 2q + 1
-// -- instead of replicated in all of them.  Per step: all-gather the position (8 v_mov_b32_dpp row_share), the row
+// -- instead of replicated in all of them.  Per step: all-gather the position (4 v_mov_b64_dpp row_newbcast), the row
 // pass (unchanged), a reduce-scatter of the 8 gradient sums (16 v_add_f32_dpp instead of the all-reduce's 32) and
-// kick + drift on ONE coordinate pair (3 v_pk_fma_f32 instead of 12): 27 instructions where there were 44, of ~190.
+// kick + drift on ONE coordinate pair (3 v_pk_fma_f32 instead of 12): 23 instructions where there were 44, of 173.
+// (Two steps per loop trip were measured and not kept: the trip loses a compare and a branch, but the first step's kick and
+//  drift then need the wait states the branch and the counter update provided, and the kernel ran SLOWER than with the plain
+//  loop -- profiles/r10_interior_slots.txt.)
 // On entry xk = k * position (all lanes), pm = momentum after the first half kick; on exit both are replicated again.
 template <int R>
 __device__ __forceinline__ void hmc_interior_rs16(const RegRowPairs<8, R, 16>& rows, const float (&d)[8], const float (&e)[8],
@@ -186,7 +189,7 @@ __device__ __forceinline__ void hmc_interior_rs16(const RegRowPairs<8, R, 16>& r
 // group for the whole launch (quad q owns coordinates 2q, 2q + 1), as hmc_interior_rs16 does inside a trajectory:
 // proposal, drift terms, proposal-density difference and the accept select act on ONE coordinate pair per lane
 // (12 packed ops instead of 45), the gradient is reduce-scattered (16 DPP adds instead of 32), the proposal is
-// all-gathered for the row pass (8 row_share moves), scalars over the coordinates are summed across the quads with
+// all-gathered for the row pass (4 64-bit row_newbcast moves), scalars over the coordinates are summed across the quads with
 // two symmetric DPP adds.  With two waves per SIMD (8192 chains) the saved instructions are saved time.
 // Same Philox stream, same accept rule (fit-np-mala.py:61-78, fit-numpy.py:53-62) as k_chain.
 template <int R, int KIND>
