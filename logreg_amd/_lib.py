@@ -106,9 +106,22 @@ PREDICT_SYMBOLS = {
     "lr_predict_destroy": (None, [_vp]),
 }
 
+ACF_MAX_LAG = 255  # LR_ACF_MAX_LAG
+ACF_HEAD_ROWS = 3  # rows of the table ahead of the autocovariances: LR_ACF_ROWS(K) = K + 4
+# name -> (restype, argtypes); every symbol include/logreg_hip_acf.h declares.  A table of its own like PREDICT_SYMBOLS, bound on first
+# use (load_acf)
+ACF_SYMBOLS = {
+    "lr_acf_create": (C.c_int, [C.c_int, _i32, _i64, _i32, _i32, C.POINTER(_vp)]),
+    "lr_acf_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_acf_result": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i64)]),
+    "lr_acf_reset": (C.c_int, [_vp]),
+    "lr_acf_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _predict = None
+_acf = None
 
 
 def bind_nuts(L):
@@ -145,6 +158,24 @@ def bind_predict(L):
 def load_predict():
     """The library with the prediction entry points bound (the same liblogreg_hip.so as load())."""
     return bind_predict(load())
+
+
+def bind_acf(L):
+    """`L` (a loaded library handle) with the autocorrelation entry points bound; resolved once per handle."""
+    global _acf
+    if _acf is L:
+        return L
+    for name, (res, args) in ACF_SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+        fn.restype = res
+        fn.argtypes = args
+    _acf = L
+    return L
+
+
+def load_acf():
+    """The library with the autocorrelation entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_acf(load())
 
 
 def load():

@@ -6,6 +6,7 @@
 #include "../../include/logreg_hip.h"
 #include "../../include/logreg_hip_nuts.h"
 #include "../../include/logreg_hip_predict.h"
+#include "../../include/logreg_hip_acf.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "lr_inst.h"
+#include "lr_acf.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
 #include "lr_hessian.h"
@@ -878,6 +880,163 @@ void lr_predict_destroy(lr_predict* pp) {
     for (void* q : {(void*)pp->d_sign, (void*)pp->d_acc, pp->d_part, pp->d_in, pp->d_pad})
         if (q) (void)hipFree(q);
     delete pp;
+}
+
+// ---- autocorrelation and Geyer ESS of the kept draws (include/logreg_hip_acf.h; kernels: lr_acf.h) ------------------------------------
+}  // extern "C"
+struct lr_acf {
+    int device = 0;
+    int dtype = LR_F32;
+    int64_t C = 0, NS = 0;  // chains, series = C p
+    int p = 0, K = 0;
+    int64_t n = 0;               // time steps folded in
+    hipStream_t last = nullptr;  // stream of the last accumulate call
+    double* d_state = nullptr;   // S [NS][K+1] | head [NS][K] | tail [NS][K] | total [NS] | x0 [NS]
+    size_t state_bytes = 0;
+    // grow-only workspaces: host blocks staged on the device; V, the workgroup partials and the table of lr_acf_result
+    void* d_in = nullptr;  size_t in_bytes = 0;
+    void* d_ws = nullptr;  size_t ws_bytes = 0;
+    size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
+    double* S() const { return d_state; }
+    double* head() const { return d_state + (size_t)NS * (K + 1); }
+    double* tail() const { return head() + (size_t)NS * K; }
+    double* total() const { return tail() + (size_t)NS * K; }
+    double* x0() const { return total() + (size_t)NS; }
+};
+namespace {
+static_assert(LR_ACF_MAX_LAG == lr::kAcfMaxLag, "largest lag");
+static_assert(LR_ACF_ROWS(0) == lr::kAcfHeadRows + 1, "table rows");
+
+int acf_grow(void** p, size_t* have, size_t want, const char* what) {
+    if (*have >= want) return LR_OK;
+    void* q = nullptr;
+    if (hipMalloc(&q, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_acf: allocating %zu bytes of %s failed", want, what);
+    if (*p) (void)hipFree(*p);  // (hipFree waits for the work that still reads it)
+    *p = q;
+    *have = want;
+    return LR_OK;
+}
+
+template <typename T>
+int acf_launch(lr_acf* a, const void* d_block, int64_t k, hipStream_t st) {
+    const dim3 grid((unsigned)((a->NS + lr::kAcfTile - 1) / lr::kAcfTile)), blk(lr::kAcfBlock);
+    const size_t lds = (size_t)lr::kAcfTile * lr::acf_row_doubles(a->K) * sizeof(double);
+    const T* b = static_cast<const T*>(d_block);
+    switch (a->K / 64 + 1) {  // lags per lane
+#define LR_ACF_CASE(NL) \
+    case NL: hipLaunchKernelGGL((lr::k_acf_accumulate<T, NL>), grid, blk, lds, st, b, k, a->NS, a->K, a->n, a->S(), a->total(), a->x0(), a->head(), a->tail()); break;
+        LR_ACF_CASE(1) LR_ACF_CASE(2) LR_ACF_CASE(3) LR_ACF_CASE(4)
+#undef LR_ACF_CASE
+    }
+    LR_HIP(hipGetLastError());
+    a->n += k;
+    return LR_OK;
+}
+}  // namespace
+extern "C" {
+
+int lr_acf_create(int device, int32_t dtype, int64_t C, int32_t p, int32_t max_lag, lr_acf** out) {
+    if (!out) return fail(LR_ERR_INVALID, "lr_acf_create: out is NULL");
+    if (C <= 0 || p <= 0) return fail(LR_ERR_INVALID, "lr_acf_create: C and p must be positive (got %lld, %d)", (long long)C, p);
+    if (max_lag < 1 || max_lag > LR_ACF_MAX_LAG || max_lag % 2 == 0)
+        return fail(LR_ERR_INVALID, "lr_acf_create: max_lag must be odd and in 1..%d (got %d)", LR_ACF_MAX_LAG, max_lag);
+    if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_acf_create: dtype must be LR_F32 or LR_F64");
+    if (C > (0x7FFFFFFFll * lr::kAcfTile) / p) return fail(LR_ERR_UNSUPPORTED, "lr_acf_create: %lld x %d series are beyond the launch grid", (long long)C, p);
+    int ndev = 0;
+    LR_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_acf_create: device %d not available (%d visible)", device, ndev);
+    LR_HIP(hipSetDevice(device));
+    lr_acf* a = new lr_acf();
+    a->device = device;
+    a->dtype = dtype;
+    a->C = C;
+    a->p = p;
+    a->K = max_lag;
+    a->NS = C * p;
+    a->state_bytes = (size_t)a->NS * (3 * (size_t)max_lag + 3) * sizeof(double);
+    if (hipMalloc((void**)&a->d_state, a->state_bytes) != hipSuccess) {
+        const size_t want = a->state_bytes;
+        delete a;
+        return fail(LR_ERR_NOMEM, "lr_acf_create: allocating %zu bytes of state failed", want);
+    }
+    hipError_t e = hipMemsetAsync(a->d_state, 0, a->state_bytes, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        lr_acf_destroy(a);
+        return fail(LR_ERR_HIP, "lr_acf_create: clearing the state failed: %s", hipGetErrorString(e));
+    }
+    *out = a;
+    return LR_OK;
+}
+
+int lr_acf_accumulate(lr_acf* a, const void* block, int64_t k, int32_t on_device, void* stream) {
+    if (!a || !block) return fail(LR_ERR_INVALID, "lr_acf_accumulate: accumulator / block is NULL");
+    if (k <= 0) return fail(LR_ERR_INVALID, "lr_acf_accumulate: k must be positive (got %lld)", (long long)k);
+    LR_HIP(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t row = (size_t)a->NS * a->esize();
+    // host blocks go through a staging buffer in pieces of at most 256 MB, sized before anything is folded in
+    const int64_t piece = on_device ? k : std::max<int64_t>(1, (int64_t)((size_t(256) << 20) / row));
+    if (!on_device)
+        if (const int rc = acf_grow(&a->d_in, &a->in_bytes, (size_t)std::min(piece, k) * row, "staged draws")) return rc;
+    a->last = st;
+    for (int64_t t0 = 0; t0 < k; t0 += piece) {
+        const int64_t kb = std::min(piece, k - t0);
+        const void* src = static_cast<const unsigned char*>(block) + (size_t)t0 * row;
+        if (!on_device) {
+            LR_HIP(hipMemcpyAsync(a->d_in, src, (size_t)kb * row, hipMemcpyHostToDevice, st));
+            src = a->d_in;
+        }
+        if (const int rc = a->dtype == LR_F32 ? acf_launch<float>(a, src, kb, st) : acf_launch<double>(a, src, kb, st)) return rc;
+    }
+    if (!on_device) LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_acf_result(lr_acf* a, double* sums, double* ess_chain, int64_t* n_draws) {
+    if (!a || !sums) return fail(LR_ERR_INVALID, "lr_acf_result: accumulator / sums is NULL");
+    LR_HIP(hipSetDevice(a->device));
+    const int64_t rows = LR_ACF_ROWS(a->K), cells = rows * a->p, nblocks = (a->C + 255) / 256;
+    if (n_draws) *n_draws = a->n;
+    if (a->n == 0) {
+        for (int64_t e = 0; e < cells; ++e) sums[e] = NAN;
+        if (ess_chain)
+            for (int64_t e = 0; e < a->NS; ++e) ess_chain[e] = NAN;
+        return LR_OK;
+    }
+    const size_t v_doubles = (size_t)rows * a->NS, part_doubles = (size_t)nblocks * cells;
+    if (const int rc = acf_grow(&a->d_ws, &a->ws_bytes, (v_doubles + part_doubles + (size_t)cells) * sizeof(double), "result workspace")) return rc;
+    double* V = static_cast<double*>(a->d_ws);
+    double* part = V + v_doubles;
+    double* d_sums = part + part_doubles;
+    hipStream_t st = a->last;
+    hipLaunchKernelGGL(lr::k_acf_finish, dim3((unsigned)((a->NS + 255) / 256)), dim3(256), 0, st, a->NS, a->K, a->n, a->S(), a->total(), a->head(), a->tail(), V);
+    LR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lr::k_acf_partial, dim3((unsigned)nblocks, (unsigned)rows), dim3(256), 0, st, V, a->C, a->p, part);
+    LR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lr::k_acf_final, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, part, nblocks, cells, d_sums);
+    LR_HIP(hipGetLastError());
+    LR_HIP(hipMemcpyAsync(sums, d_sums, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ess_chain) LR_HIP(hipMemcpyAsync(ess_chain, V, (size_t)a->NS * sizeof(double), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_acf_reset(lr_acf* a) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_acf_reset: accumulator is NULL");
+    LR_HIP(hipSetDevice(a->device));
+    LR_HIP(hipMemsetAsync(a->d_state, 0, a->state_bytes, a->last));
+    LR_HIP(hipStreamSynchronize(a->last));
+    a->n = 0;
+    return LR_OK;
+}
+
+void lr_acf_destroy(lr_acf* a) {
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    for (void* q : {(void*)a->d_state, a->d_in, a->d_ws})
+        if (q) (void)hipFree(q);
+    delete a;
 }
 
 // ---- device memory / stream / event helpers -------------------------------------------------------
