@@ -118,10 +118,23 @@ ACF_SYMBOLS = {
     "lr_acf_destroy": (None, [_vp]),
 }
 
+MARG_MAX_BINS = 1024  # LR_MARG_MAX_BINS
+MARG_ROWS = 6  # LR_MARG_ROWS: min, max, S1..S4; a coordinate has LR_MARG_COLS(B) = B + 3 columns (underflow, B bins, overflow, NaN)
+# name -> (restype, argtypes); every symbol include/logreg_hip_marginals.h declares.  A table of its own like ACF_SYMBOLS, bound on first
+# use (load_marginals)
+MARG_SYMBOLS = {
+    "lr_marg_create": (C.c_int, [C.c_int, _i32, _i64, _i32, _i32, _vp, _vp, C.POINTER(_vp)]),
+    "lr_marg_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_marg_result": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i64)]),
+    "lr_marg_reset": (C.c_int, [_vp]),
+    "lr_marg_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _predict = None
 _acf = None
+_marg = None
 
 
 def bind_nuts(L):
@@ -176,6 +189,24 @@ def bind_acf(L):
 def load_acf():
     """The library with the autocorrelation entry points bound (the same liblogreg_hip.so as load())."""
     return bind_acf(load())
+
+
+def bind_marginals(L):
+    """`L` (a loaded library handle) with the marginals entry points bound; resolved once per handle."""
+    global _marg
+    if _marg is L:
+        return L
+    for name, (res, args) in MARG_SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+        fn.restype = res
+        fn.argtypes = args
+    _marg = L
+    return L
+
+
+def load_marginals():
+    """The library with the marginals entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_marginals(load())
 
 
 def load():

@@ -68,7 +68,8 @@ def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(INCLUDE, "logreg_hip.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_nuts.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_predict.h"),
-                                                                        os.path.join(INCLUDE, "logreg_hip_acf.h")]
+                                                                        os.path.join(INCLUDE, "logreg_hip_acf.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_marginals.h")]
 
 
 def _dirs(alt: bool):

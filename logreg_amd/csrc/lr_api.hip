@@ -7,6 +7,7 @@
 #include "../../include/logreg_hip_nuts.h"
 #include "../../include/logreg_hip_predict.h"
 #include "../../include/logreg_hip_acf.h"
+#include "../../include/logreg_hip_marginals.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -21,6 +22,7 @@
 
 #include "lr_inst.h"
 #include "lr_acf.h"
+#include "lr_marginals.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
 #include "lr_hessian.h"
@@ -1037,6 +1039,190 @@ void lr_acf_destroy(lr_acf* a) {
     for (void* q : {(void*)a->d_state, a->d_in, a->d_ws})
         if (q) (void)hipFree(q);
     delete a;
+}
+
+// ---- marginal histograms, min / max and power sums of the kept draws (include/logreg_hip_marginals.h; kernels: lr_marginals.h) ---------
+}  // extern "C"
+struct lr_marg {
+    int device = 0;
+    int dtype = LR_F32;
+    int64_t C = 0, NS = 0;  // chains, series = C p
+    int p = 0, bins = 0, pt = 0;  // pt: coordinates per LDS table (= p: the flat lane map)
+    int64_t n = 0;               // time steps folded in
+    hipStream_t last = nullptr;  // stream of the last accumulate call
+    unsigned long long* d_state = nullptr;  // counts [p][bins+3] | sums [NS][4] | mn [NS] | mx [NS] | grid [5][p], 8 bytes each
+    // grow-only workspaces: host blocks staged on the device; the workgroup partials and the table of lr_marg_result
+    void* d_in = nullptr;  size_t in_bytes = 0;
+    void* d_ws = nullptr;  size_t ws_bytes = 0;
+    size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
+    int64_t cells() const { return (int64_t)p * LR_MARG_COLS(bins); }
+    unsigned long long* counts() const { return d_state; }
+    double* sums() const { return reinterpret_cast<double*>(d_state + cells()); }
+    double* mn() const { return sums() + 4 * (size_t)NS; }
+    double* mx() const { return mn() + (size_t)NS; }
+    double* grid() const { return mx() + (size_t)NS; }
+    size_t state_words() const { return (size_t)cells() + 6 * (size_t)NS + 5 * (size_t)p; }
+};
+namespace {
+static_assert(LR_MARG_MAX_BINS == lr::kMargMaxBins, "most bins");
+static_assert(LR_MARG_ROWS == lr::kMargRows, "table rows");
+static_assert(sizeof(unsigned long long) == sizeof(uint64_t) && sizeof(double) == 8, "one state word is 8 bytes");
+static_assert((size_t)lr::kMargBlock * lr::kMargMaxSteps < (size_t(1) << 32), "an LDS counter cannot wrap within a launch");
+
+int marg_grow(void** p, size_t* have, size_t want, const char* what) {
+    if (*have >= want) return LR_OK;
+    void* q = nullptr;
+    if (hipMalloc(&q, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_marg: allocating %zu bytes of %s failed", want, what);
+    if (*p) (void)hipFree(*p);  // (hipFree waits for the work that still reads it)
+    *p = q;
+    *have = want;
+    return LR_OK;
+}
+
+int marg_clear(lr_marg* m, hipStream_t st) {
+    const int64_t most = std::max(m->cells(), m->NS);
+    hipLaunchKernelGGL(lr::k_marg_init, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, st, m->NS, m->cells(), m->counts(), m->sums(), m->mn(), m->mx());
+    LR_HIP(hipGetLastError());
+    LR_HIP(hipStreamSynchronize(st));
+    m->n = 0;
+    return LR_OK;
+}
+
+template <typename T>
+int marg_launch(lr_marg* m, const void* d_block, int64_t k, hipStream_t st) {
+    int64_t blocks;
+    if (m->pt == m->p) {
+        blocks = (m->NS + lr::kMargBlock - 1) / lr::kMargBlock;
+    } else {
+        const int64_t per = lr::kMargBlock / m->pt;
+        blocks = ((m->C + per - 1) / per) * ((m->p + m->pt - 1) / m->pt);
+    }
+    const size_t lds = (size_t)std::min(m->pt, m->p) * LR_MARG_COLS(m->bins) * sizeof(unsigned int);
+    const T* b = static_cast<const T*>(d_block);
+    for (int64_t t0 = 0; t0 < k; t0 += lr::kMargMaxSteps) {  // (an LDS counter takes at most 256 x kMargMaxSteps increments)
+        const int64_t kb = std::min<int64_t>(lr::kMargMaxSteps, k - t0);
+        hipLaunchKernelGGL((lr::k_marg_accumulate<T>), dim3((unsigned)blocks), dim3(lr::kMargBlock), lds, st, b + (size_t)t0 * m->NS, kb, m->C, m->p, m->bins,
+                           m->pt, m->grid(), m->counts(), m->sums(), m->mn(), m->mx());
+        LR_HIP(hipGetLastError());
+    }
+    m->n += k;
+    return LR_OK;
+}
+}  // namespace
+extern "C" {
+
+int lr_marg_create(int device, int32_t dtype, int64_t C, int32_t p, int32_t bins, const double* lo, const double* hi, lr_marg** out) {
+    if (!out || !lo || !hi) return fail(LR_ERR_INVALID, "lr_marg_create: out / lo / hi is NULL");
+    if (C <= 0 || p <= 0) return fail(LR_ERR_INVALID, "lr_marg_create: C and p must be positive (got %lld, %d)", (long long)C, p);
+    if (bins < 1 || bins > LR_MARG_MAX_BINS) return fail(LR_ERR_INVALID, "lr_marg_create: bins must be in 1..%d (got %d)", LR_MARG_MAX_BINS, bins);
+    if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_marg_create: dtype must be LR_F32 or LR_F64");
+    for (int j = 0; j < p; ++j)
+        if (!(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] < hi[j] && std::isfinite(hi[j] - lo[j])))
+            return fail(LR_ERR_INVALID, "lr_marg_create: the grid of coordinate %d must be finite with lo < hi (got %g, %g)", j, lo[j], hi[j]);
+    const int pt = lr::marg_rows(p, bins);
+    const int64_t per = pt == p ? 1 : lr::kMargBlock / pt, ntile = pt == p ? 1 : (p + pt - 1) / pt;
+    if (C > 0x7FFFFFFFll * lr::kMargBlock / p || (C + per - 1) / per > 0x7FFFFFFFll / ntile)
+        return fail(LR_ERR_UNSUPPORTED, "lr_marg_create: %lld x %d series are beyond the launch grid", (long long)C, p);
+    int ndev = 0;
+    LR_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_marg_create: device %d not available (%d visible)", device, ndev);
+    LR_HIP(hipSetDevice(device));
+    lr_marg* m = new lr_marg();
+    m->device = device;
+    m->dtype = dtype;
+    m->C = C;
+    m->p = p;
+    m->bins = bins;
+    m->pt = pt;
+    m->NS = C * p;
+    const size_t want = m->state_words() * 8;
+    if (hipMalloc((void**)&m->d_state, want) != hipSuccess) {
+        delete m;
+        return fail(LR_ERR_NOMEM, "lr_marg_create: allocating %zu bytes of state failed", want);
+    }
+    std::vector<double> g(5 * (size_t)p);
+    for (int j = 0; j < p; ++j) {
+        g[j] = lo[j];
+        g[(size_t)p + j] = (double)bins / (hi[j] - lo[j]);
+        g[2 * (size_t)p + j] = (lo[j] + hi[j]) / 2.0;
+        g[3 * (size_t)p + j] = 2.0 / (hi[j] - lo[j]);
+        g[4 * (size_t)p + j] = hi[j];
+    }
+    hipError_t e = hipMemcpy(m->grid(), g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess || marg_clear(m, nullptr) != LR_OK) {
+        lr_marg_destroy(m);
+        return e != hipSuccess ? fail(LR_ERR_HIP, "lr_marg_create: copying the grid failed: %s", hipGetErrorString(e)) : LR_ERR_HIP;
+    }
+    *out = m;
+    return LR_OK;
+}
+
+int lr_marg_accumulate(lr_marg* m, const void* block, int64_t k, int32_t on_device, void* stream) {
+    if (!m || !block) return fail(LR_ERR_INVALID, "lr_marg_accumulate: accumulator / block is NULL");
+    if (k <= 0) return fail(LR_ERR_INVALID, "lr_marg_accumulate: k must be positive (got %lld)", (long long)k);
+    LR_HIP(hipSetDevice(m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t row = (size_t)m->NS * m->esize();
+    // host blocks go through a staging buffer in pieces of at most 256 MB, sized before anything is folded in
+    const int64_t piece = on_device ? k : std::max<int64_t>(1, (int64_t)((size_t(256) << 20) / row));
+    if (!on_device)
+        if (const int rc = marg_grow(&m->d_in, &m->in_bytes, (size_t)std::min(piece, k) * row, "staged draws")) return rc;
+    m->last = st;
+    for (int64_t t0 = 0; t0 < k; t0 += piece) {
+        const int64_t kb = std::min(piece, k - t0);
+        const void* src = static_cast<const unsigned char*>(block) + (size_t)t0 * row;
+        if (!on_device) {
+            LR_HIP(hipMemcpyAsync(m->d_in, src, (size_t)kb * row, hipMemcpyHostToDevice, st));
+            src = m->d_in;
+        }
+        if (const int rc = m->dtype == LR_F32 ? marg_launch<float>(m, src, kb, st) : marg_launch<double>(m, src, kb, st)) return rc;
+    }
+    if (!on_device) LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_marg_result(lr_marg* m, uint64_t* counts, double* table, int64_t* n_draws) {
+    if (!m) return fail(LR_ERR_INVALID, "lr_marg_result: accumulator is NULL");
+    LR_HIP(hipSetDevice(m->device));
+    const int64_t tcells = (int64_t)LR_MARG_ROWS * m->p, nblocks = (m->C + 255) / 256;
+    if (n_draws) *n_draws = m->n;
+    if (m->n == 0) {
+        if (counts) std::fill(counts, counts + m->cells(), uint64_t(0));
+        if (table)
+            for (int64_t e = 0; e < tcells; ++e) table[e] = NAN;
+        return LR_OK;
+    }
+    hipStream_t st = m->last;
+    if (table) {
+        if (const int rc = marg_grow(&m->d_ws, &m->ws_bytes, (size_t)(nblocks + 1) * tcells * sizeof(double), "result workspace")) return rc;
+        double* part = static_cast<double*>(m->d_ws);
+        double* d_table = part + (size_t)nblocks * tcells;
+        hipLaunchKernelGGL(lr::k_marg_partial, dim3((unsigned)nblocks, (unsigned)LR_MARG_ROWS), dim3(256), 0, st, m->sums(), m->mn(), m->mx(), m->C, m->p, part);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(lr::k_marg_final, dim3((unsigned)((tcells + 255) / 256)), dim3(256), 0, st, part, nblocks, m->p, d_table);
+        LR_HIP(hipGetLastError());
+        LR_HIP(hipMemcpyAsync(table, d_table, (size_t)tcells * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (counts) LR_HIP(hipMemcpyAsync(counts, m->counts(), (size_t)m->cells() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    if (table)
+        for (int j = 0; j < m->p; ++j)
+            if (table[j] > table[m->p + j]) table[j] = table[m->p + j] = NAN;  // +inf > -inf: the coordinate has no non-NaN draw
+    return LR_OK;
+}
+
+int lr_marg_reset(lr_marg* m) {
+    if (!m) return fail(LR_ERR_INVALID, "lr_marg_reset: accumulator is NULL");
+    LR_HIP(hipSetDevice(m->device));
+    return marg_clear(m, m->last);
+}
+
+void lr_marg_destroy(lr_marg* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    for (void* q : {(void*)m->d_state, m->d_in, m->d_ws})
+        if (q) (void)hipFree(q);
+    delete m;
 }
 
 // ---- device memory / stream / event helpers -------------------------------------------------------

@@ -603,7 +603,7 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
-         autocorr=None, predictive=None):
+         autocorr=None, marginals=None, predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -634,6 +634,11 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     it on the device, in time order, before the block is copied or freed (under `summary_only=True` the block lives only that long);
     the summary dict -- or, with `return_info=True`, the info dict -- gains `"autocorr": autocorr.result()` (Geyer ESS per chain and
     pooled, the pooled autocorrelation).  Chains, states, statistics and accept counts are those of the same call without it.
+    `marginals` (fused kernels): a `Marginals` of the run's chain count, p, dtype and device.  Every chunk's block of kept samples is
+    folded into it on the device exactly where `autocorr` is; the summary dict -- or, with `return_info=True`, the info dict -- gains
+    `"marginals": marginals.result()` (min/max, mean, variance, skewness, kurtosis, the histograms; `quantile`, `interval` and `hpd` of
+    logreg_amd.marginals read quantiles and credible intervals off it).  Chains, states, statistics and accept counts are those of the
+    same call without it.
     `plan_chains`, `plan_first`: chain count to plan the kernel variant for and the global id of that run's first chain (a shard of
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
@@ -642,6 +647,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             raise ValueError("predictive= needs a fused kernel (the closures of a LogReg)")
         if autocorr is not None:
             raise ValueError("autocorr= needs a fused kernel (the closures of a LogReg)")
+        if marginals is not None:
+            raise ValueError("marginals= needs a fused kernel (the closures of a LogReg)")
         return _mcmc_generic(init, kernel, thin, iters, verb)
     if predictive is not None and getattr(predictive, "model", None) is not kernel.model:
         raise ValueError("predictive= must be a PosteriorPredictive of the kernel's own model")
@@ -655,6 +662,15 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         want = (int(np.atleast_2d(init).shape[0]), km.p, np.dtype(km.np_dtype), km.device)
         if (autocorr.chains, autocorr.p, autocorr.dtype, autocorr.device) != want:
             raise ValueError(f"autocorr= is for {autocorr.chains} chains x p={autocorr.p} of {autocorr.dtype.name} on device {autocorr.device}; "
+                             f"this run has {want[0]} chains x p={want[1]} of {want[2].name} on device {want[3]}")
+    if marginals is not None:  # refused before anything runs
+        from .marginals import Marginals
+        km = kernel.model
+        if not isinstance(marginals, Marginals):
+            raise ValueError(f"marginals= must be a Marginals; got {type(marginals).__name__}")
+        want = (int(np.atleast_2d(init).shape[0]), km.p, np.dtype(km.np_dtype), km.device)
+        if (marginals.chains, marginals.p, marginals.dtype, marginals.device) != want:
+            raise ValueError(f"marginals= is for {marginals.chains} chains x p={marginals.p} of {marginals.dtype.name} on device {marginals.device}; "
                              f"this run has {want[0]} chains x p={want[1]} of {want[2].name} on device {want[3]}")
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
@@ -679,13 +695,15 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         done = 0
         while done < iters:
             k = min(chunk, iters - done)
-            if predictive is None and autocorr is None:
+            if predictive is None and autocorr is None and marginals is None:
                 cs.advance(k, thin, keep=False)
                 cs.sync()
             else:  # the chunk's samples exist on the device just long enough to be folded into the accumulator(s)
                 out = cs.advance(k, thin, keep=True)
                 if autocorr is not None:
                     autocorr.update(out, stream=cs.stream)
+                if marginals is not None:
+                    marginals.update(out, stream=cs.stream)
                 if predictive is not None:
                     predictive.update(out, stream=cs.stream)
                 cs.sync()
@@ -705,6 +723,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
         if autocorr is not None:
             res["autocorr"] = autocorr.result()
+        if marginals is not None:
+            res["marginals"] = marginals.result()
         if predictive is not None:
             res["predictive"] = predictive
         return res
@@ -717,6 +737,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         out = cs.advance(k, thin, keep=True)
         if autocorr is not None:
             autocorr.update(out, stream=cs.stream)
+        if marginals is not None:
+            marginals.update(out, stream=cs.stream)
         if predictive is not None:
             predictive.update(out, stream=cs.stream)
         cs.sync()
@@ -739,6 +761,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             info["proposal"] = kernel.proposal
         if autocorr is not None:
             info["autocorr"] = autocorr.result()
+        if marginals is not None:
+            info["marginals"] = marginals.result()
         return res, info
     return res
 
