@@ -35,10 +35,16 @@ ARCH = "gfx950"
 # into v_pk_add_f32 and lose the fused v_add_f32_dpp form (16 more instructions per evaluation)
 # -amdgpu-sched-strategy=max-ilp: the kernels run one or two waves per SIMD by design, so latency hiding has
 # to come from instruction-level parallelism, not occupancy (HMC hot loop: +7 % over the default strategy)
-# -falign-loops=64: the 1.4 KB leapfrog loop of the fused HMC kernel runs one wave per SIMD, nothing hides its
+# -falign-loops=64: the 1.3 KB leapfrog loop of the fused HMC kernel runs one wave per SIMD, nothing hides its
 # instruction fetch; when an unrelated edit elsewhere in the file moved the loop head to an address = 4 mod 8 the
-# kernel lost 10 % (0.444 -> 0.489 ms per launch, identical instructions).  With every loop head on a 64-byte
-# line the time no longer depends on what precedes the loop (8 / 16 / 32 / 64 / 128: 0.451 / 0.442 / 0.450 / 0.443 / 0.447 ms).
+# kernel lost 10 % (0.444 -> 0.489 ms per launch, identical instructions); 8 / 16 / 32 / 64 / 128 all gave the same time
+# (0.451 / 0.442 / 0.450 / 0.443 / 0.447 ms).  The mechanism, as measured (tools/valu_ops_rate.hip, profiles/r13_loop_layout.txt): it is
+# not the branch target.  An 8-byte instruction that starts at 4 mod 8 costs ONE wave per SIMD 0.9 cycles more than the same
+# instruction at 0 mod 8 (v_pk_fma_f32 6.36 against 5.41 cycles, v_add_f32_dpp 6.02 / 5.11, VOP3 v_fma_f32 6.06 / 5.14; nothing from
+# two waves per SIMD on), every one of them, and the edit had flipped which of the body's 137 eight-byte instructions those were
+# (47 <-> 90).  The flag fixes the parity of the loop HEAD only; inside the loop every lone 4-byte instruction flips the parity of
+# what follows it, so hmc_interior_rs16 is written to hold none (lr_device.h group16_reduce_scatter8_kick, the VOP3 helpers), and
+# tests/test_loop_layout_cpu.py keeps the headline loop at 0 eight-byte instructions at 4 mod 8 (tools/loop_layout.py reports them).
 # -amdgpu-mfma-vgpr-form: MFMA results in VGPRs.  In the AGPR form the register allocator rotated the 32 gradient
 # accumulators of the wide kernels through VGPRs on every trip of the block loop (48 v_accvgpr_read + 32
 # v_accvgpr_write per 24 MFMAs: 184 -> 104 instructions per block with the flag); no kernel here needs more than

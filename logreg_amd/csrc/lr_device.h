@@ -445,6 +445,34 @@ __device__ __forceinline__ double fma_t(double a, double b, double c) { return _
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 __device__ __forceinline__ double fast_exp(double x) { return exp(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+// The same instructions in the 8-byte VOP3 encoding, for the loop that one wave per SIMD runs with nothing to hide its instruction fetch
+// behind (hmc_interior_rs16): an 8-byte instruction that starts at 4 mod 8 costs such a wave up to a cycle more than one at 0 mod 8
+// (profiles/r13_loop_layout.txt), and a lone 4-byte instruction moves every packed instruction behind it to 4 mod 8.  The unpaired
+// row's add, exp, add, rcp are such lone instructions; VOP3 issues in the time of the 4-byte form (5.03 / 8.98 / 9.01 cycles against
+// 5.03 / 8.97 / 8.99).  Not volatile: the scheduler places them like the builtins.  (The exponentials and reciprocals of the twisted
+// pairs stay builtins: as two-instruction asm statements they are adjacent by construction, but the compiler counts no wait state
+// for an asm statement, so a run of them in front of a reader of a packed result gets an s_nop 0 that nothing needs -- a lone 4-byte
+// instruction again.  tests/test_loop_layout_cpu.py asserts that the loop's 4-byte vector instructions come in adjacent pairs.)
+__device__ __forceinline__ float add_vop3(float a, float b) {
+    float r;
+    asm("v_add_f32_e64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float add_one_vop3(float a) {
+    float r;
+    asm("v_add_f32_e64 %0, 1.0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ float exp2_vop3(float a) {
+    float r;
+    asm("v_exp_f32_e64 %0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ float rcp_vop3(float a) {
+    float r;
+    asm("v_rcp_f32_e64 %0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
 // 1 / x for x in [1, inf]: hardware seed + two Newton steps (6 instructions; the IEEE division the compiler expands `1.0 / x` to is
 // 11: v_div_scale x2, v_rcp, 5 fma, v_div_fmas, v_div_fixup).  Error a few ulp -- far below what the tests ask of the float64 path
 // (1e-11).  x = inf (exp overflowed) is clamped so that the Newton residual stays finite: the result is 1e-300 instead of 0.
@@ -670,7 +698,8 @@ template <typename T, int P> __device__ __forceinline__ void vscale(T s, const T
 // Nothing follows the last add: the callers' next use of u0 / u1 is an ordinary (non-DPP) operand -- the prior's
 // v_pk_fma_f32, a v_cvt_f64_f32 -- for which the compiler pads what it needs itself.  A caller that read u0 or u1 through
 // DPP next would have to wait two states first.  The order of the additions is the one of the four levels above: every
-// sum has the same operands in the same association whatever the issue order.
+// sum has the same operands in the same association whatever the issue order.  (Callers: MALA and RWMH, two waves per SIMD at 8192 chains, and
+// the mixed kernel.  The one-wave HMC loop uses group16_reduce_scatter8_kick below, the same additions laid out on 8-byte boundaries.)
 __device__ __forceinline__ void group16_reduce_scatter8(const float (&v)[8], float& u0, float& u1) {
     float r0, r1, r2, r3, s0, s1;
     asm volatile(
@@ -695,6 +724,57 @@ __device__ __forceinline__ void group16_reduce_scatter8(const float (&v)[8], flo
         "v_add_f32_dpp %7, %7, %7 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
         : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(s0), "=&v"(s1), "=&v"(u0), "=&v"(u1)
         : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+}
+// The same 16 additions laid out for ONE wave per SIMD, with what hmc_interior_rs16 does with the two totals -- the prior's term and the
+// kick, two v_pk_fma_f32 -- in the same statement:  p += st * (u - x * e),  u = (u0, u1).  For one wave an 8-byte instruction at 4 mod 8
+// costs up to a cycle (profiles/r13_loop_layout.txt).  Every 8-byte instruction of this block starts at 0 mod 8, whatever precedes
+// the block:
+//   - the two leading wait states are s_nop 1 and .p2align 3: where the block starts at 0 mod 8 (the headline kernel) the assembler
+//     adds an s_nop 0 and the pair is 8 bytes, where it starts at 4 mod 8 it adds nothing and the adds start at 0 mod 8 all the same;
+//   - level 2 finishes s0 before it starts s1 (reads r0, r2, r1, r3: at least two instructions after the last write of each), so
+//     level 3's first add needs no pad; the second add of level 3 and the second add of level 4 have one instruction of their own
+//     chain in front of them and take an 8-byte v_nop (VOP3 encoding: 5.07 cycles against the 4.27 of s_nop 0; the 4-byte v_nop
+//     costs 22.7) as the second wait state:  L3a, v_nop, L3b, L4a, v_nop, L4b;
+//   - the kick reads the prior term's packed result: one wait state, a third v_nop.  Left to the compiler the prior and the kick
+//     cost two 4-byte s_nop 0 (the result of an asm statement read by the next instruction, a packed result read by the next),
+//     each of which moves what follows to 4 mod 8;
+//   - the totals meet in v[254:255]: a 32-bit DPP add cannot name one half of a 64-bit asm operand and the packed multiply-add
+//     needs the pair, so the pair is a fixed one, above every register the kernels of this loop use (250 at 16 rows per lane).
+//     The clobber list is all that keeps the allocator off the pair: both kernels now declare 256 VGPRs, the most a wave can name, so
+//     an instantiation that needs more than 254 registers of its own spills -- which the build's no-scratch gate refuses
+//     (logreg_amd/build.py resource_gate).  A wider loop needs another meeting place, not a higher pair.
+// Same operands in the same association as above and as the compiler's own two multiply-adds: the bytes are the same.  With two waves
+// or more per SIMD (MALA, RWMH) the fetch is hidden, s_nop 0 costs half a vector slot and the form above is the cheaper one.
+__device__ __forceinline__ void group16_reduce_scatter8_kick(const float (&v)[8], const f32x2& x, const f32x2& e, const f32x2& st, f32x2& p) {
+    float r0, r1, r2, r3, s0, s1;
+    f32x2 g;
+    asm volatile(
+        "s_nop 1\n\t"
+        ".p2align 3\n\t"
+        "v_add_f32_dpp %0, %8, %8 row_mirror row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %1, %9, %9 row_mirror row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %2, %10, %10 row_mirror row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %3, %11, %11 row_mirror row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %0, %12, %12 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %1, %13, %13 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %2, %14, %14 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %3, %15, %15 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %4, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %4, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %5, %1, %1 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %5, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp v254, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_nop_e64\n\t"
+        "v_add_f32_dpp v255, %5, %5 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp v254, v254, v254 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_nop_e64\n\t"
+        "v_add_f32_dpp v255, v255, v255 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_pk_fma_f32 %6, %16, %17, v[254:255] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
+        "v_nop_e64\n\t"
+        "v_pk_fma_f32 %7, %18, %6, %7"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(s0), "=&v"(s1), "=&v"(g), "+v"(p)
+        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(x), "v"(e), "s"(st)
+        : "v254", "v255");
 }
 // sum over the four quads of a 16-lane row of a value that is identical inside each quad; symmetric exchanges
 // (i <-> 7 - i, then i <-> 15 - i), so every lane adds the same two numbers at each level: bit-identical in all 16
@@ -940,9 +1020,12 @@ __device__ __forceinline__ void pair_term(const f32x2 (&q)[P], const f32x2 (&bb)
 // product can only fail by OVERFLOW (positive logits summing beyond ~127 in one lane); a lane whose product overflowed takes the
 // per-row form instead -- a per-LANE select, so a chain's value never depends on which chains share its wave; the per-row pass
 // itself runs (wave-uniformly) only when some lane needs it.  Same cancellation class as the per-row form: ulp(sum ts) per lane.
-template <int P, int R, int G, bool VALUE, bool GRAD>
+// LAYOUT (gradient only; hmc_interior_rs16): the four lone instructions of an unpaired row in VOP3 encoding (add_vop3 and the rest above),
+// so that every 8-byte instruction of that loop starts at 0 mod 8.
+template <int P, int R, int G, bool VALUE, bool GRAD, bool LAYOUT = false>
 __device__ __forceinline__ void row_pairs_eval(const RegRowPairs<P, R, G>& rows, const f32x2 (&bb)[P / 2],
                                                f32x2 (&gp)[P / 2], float& v) {
+    static_assert(!LAYOUT || (GRAD && !VALUE), "the laid-out form is the interior leapfrog gradient");
     typedef f32x2 f2;
     f2 hp[P / 2];
 #pragma unroll
@@ -959,11 +1042,11 @@ __device__ __forceinline__ void row_pairs_eval(const RegRowPairs<P, R, G>& rows,
         f2 acc = rows.s[0] * bb[0];
 #pragma unroll
         for (int j = 1; j < P / 2; ++j) acc = __builtin_elementwise_fma(rows.s[j], bb[j], acc);
-        float ts = acc.x + acc.y;
+        float ts = LAYOUT ? add_vop3(acc.x, acc.y) : acc.x + acc.y;
         if constexpr (VALUE && !PROD) ts = min_keep_nan(ts, 100.0f);
-        const float d = 1.0f + ExpScale<float>::exp_scaled(ts);
+        const float d = LAYOUT ? add_one_vop3(exp2_vop3(ts)) : 1.0f + ExpScale<float>::exp_scaled(ts);
         if constexpr (GRAD) {
-            const float w = fast_rcp(d);
+            const float w = LAYOUT ? rcp_vop3(d) : fast_rcp(d);
 #pragma unroll
             for (int j = 0; j < P / 2; ++j) gp[j] = __builtin_elementwise_fma(f2{w, w}, rows.s[j], gp[j]);
         }

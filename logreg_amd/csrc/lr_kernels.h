@@ -146,6 +146,10 @@ __global__ void __launch_bounds__(256) k_eval(ModelArgs<T, P> m, EvalArgs<T> a) 
 // (Two steps per loop trip were measured and not kept: the trip loses a compare and a branch, but the first step's kick and
 //  drift then need the wait states the branch and the counter update provided, and the kernel ran SLOWER than with the plain
 //  loop -- profiles/r10_interior_slots.txt.)
+// Layout: this loop runs ONE wave per SIMD, which pays up to a cycle for every 8-byte instruction that starts at 4 mod 8, and a lone
+// 4-byte instruction moves all that follow it.  The loop holds none -- the unpaired row in VOP3 encoding (row_pairs_eval's LAYOUT),
+// reduce-scatter, prior and kick as one aligned block (group16_reduce_scatter8_kick) -- and tests/test_loop_layout_cpu.py keeps it so
+// (python tools/loop_layout.py f32 8; profiles/r13_loop_layout.txt: 47 of 137 eight-byte instructions at 4 mod 8 before, 0.371 -> 0.363 ms).
 // On entry xk = k * position (all lanes), pm = momentum after the first half kick; on exit both are replicated again.
 template <int R>
 __device__ __forceinline__ void hmc_interior_rs16(const RegRowPairs<8, R, 16>& rows, const float (&d)[8], const float (&e)[8],
@@ -164,12 +168,9 @@ __device__ __forceinline__ void hmc_interior_rs16(const RegRowPairs<8, R, 16>& r
         group16_allgather_pairs(xq, bb);
         f32x2 gpp[4];
         float unused = 0.0f;
-        row_pairs_eval<8, R, 16, false, true>(rows, bb, gpp, unused);
+        row_pairs_eval<8, R, 16, false, true, true>(rows, bb, gpp, unused);
         const float gv[8] = {gpp[0].x, gpp[0].y, gpp[1].x, gpp[1].y, gpp[2].x, gpp[2].y, gpp[3].x, gpp[3].y};
-        float u0, u1;
-        group16_reduce_scatter8(gv, u0, u1);
-        const f32x2 gq = __builtin_elementwise_fma(-xq, eq, f32x2{u0, u1});  // + prior:  g - (k q)(ivar / k)
-        pq = __builtin_elementwise_fma(st, gq, pq);                          // kick
+        group16_reduce_scatter8_kick(gv, xq, eq, st, pq);  // pq += st * (g - (k q)(ivar / k)): reduce-scatter, prior, kick
     }
     xq = __builtin_elementwise_fma(dq, pq, xq);  // the last drift (its gradient is the end-point evaluation)
     group16_allgather_pairs(xq, bb);
