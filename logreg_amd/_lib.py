@@ -130,11 +130,26 @@ MARG_SYMBOLS = {
     "lr_marg_destroy": (None, [_vp]),
 }
 
+LOO_ROWS = 5  # LR_LOO_ROWS: elpd_loo_i, khat_i, n_eff_i, lppd_i, n_tail_i
+LOO_MAX_DRAWS = 1 << 20  # LR_LOO_MAX_DRAWS
+# name -> (restype, argtypes); every symbol include/logreg_hip_loo.h declares.  A table of its own like MARG_SYMBOLS, bound on first
+# use (load_loo)
+LOO_SYMBOLS = {
+    "lr_loo_create": (C.c_int, [_vp, _i64, C.POINTER(_vp)]),
+    "lr_loo_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_loo_loglik": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "lr_loo_result": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "lr_loo_reset": (C.c_int, [_vp]),
+    "lr_loo_destroy": (None, [_vp]),
+    "lr_psis": (C.c_int, [C.c_int, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+}
+
 _lib = None
 _nuts = None
 _predict = None
 _acf = None
 _marg = None
+_loo = None
 
 
 def bind_nuts(L):
@@ -207,6 +222,24 @@ def bind_marginals(L):
 def load_marginals():
     """The library with the marginals entry points bound (the same liblogreg_hip.so as load())."""
     return bind_marginals(load())
+
+
+def bind_loo(L):
+    """`L` (a loaded library handle) with the PSIS-LOO entry points bound; resolved once per handle."""
+    global _loo
+    if _loo is L:
+        return L
+    for name, (res, args) in LOO_SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+        fn.restype = res
+        fn.argtypes = args
+    _loo = L
+    return L
+
+
+def load_loo():
+    """The library with the PSIS-LOO entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_loo(load())
 
 
 def load():

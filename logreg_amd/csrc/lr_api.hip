@@ -8,6 +8,7 @@
 #include "../../include/logreg_hip_predict.h"
 #include "../../include/logreg_hip_acf.h"
 #include "../../include/logreg_hip_marginals.h"
+#include "../../include/logreg_hip_loo.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -28,6 +29,7 @@
 #include "lr_hessian.h"
 #include "lr_mfma.h"
 #include "lr_predict.h"
+#include "lr_loo.h"
 #include "lr_stats.h"
 #include "lr_tall.h"
 #include "lr_tall_mx.h"
@@ -1223,6 +1225,236 @@ void lr_marg_destroy(lr_marg* m) {
     for (void* q : {(void*)m->d_state, m->d_in, m->d_ws})
         if (q) (void)hipFree(q);
     delete m;
+}
+
+// ---- PSIS-LOO: the pointwise log-likelihood matrix and its Pareto-smoothed leave-one-out summary (include/logreg_hip_loo.h; kernels: lr_loo.h)
+}  // extern "C"
+struct lr_loo {
+    lr_model* m = nullptr;
+    int device = 0;              // the model's (kept here: lr_loo_destroy must not need the model)
+    int64_t n = 0;               // the model's rows
+    int64_t cap = 0, ld = 0;     // max_draws; the row stride of the matrix (cap rounded up to 128 bytes)
+    size_t es = 0;               // bytes per value: the model's dtype
+    int32_t dtype = LR_F32;
+    void* d_ll = nullptr;        // [n][ld]
+    double* d_table = nullptr;   // [LR_LOO_ROWS][n]
+    int64_t S = 0;               // draws held
+    hipStream_t last = nullptr;  // stream of the last accumulate call
+    // grow-only workspaces: host draws staged on the device, draws padded to the kernel width, the matrix transposed for lr_loo_loglik
+    void* d_in = nullptr;    size_t in_bytes = 0;
+    void* d_pad = nullptr;   size_t pad_bytes = 0;
+    void* d_out = nullptr;   size_t out_bytes = 0;
+};
+namespace {
+static_assert(LR_LOO_ROWS == lr::kLooRows && LR_LOO_MAX_DRAWS == lr::kLooMaxDraws, "logreg_hip_loo.h and lr_loo.h");
+
+int loo_grow(void** p, size_t* have, size_t want, const char* what) {
+    if (*have >= want) return LR_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_loo: allocating %zu bytes of %s failed", want, what);
+    *have = want;
+    return LR_OK;
+}
+
+template <typename T, int P>
+int loo_fill(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
+    constexpr int64_t TS = lr::kLooTileBytes / (int)sizeof(T);
+    const int64_t tiles = (a->n + lr::kLooBlock - 1) / lr::kLooBlock;
+    const int64_t want_blocks = (int64_t)(a->m->cus > 0 ? a->m->cus : 256) * 4;  // four waves on every SIMD, at least 64 draws a slice
+    const int64_t sl = std::max<int64_t>(1, (want_blocks + tiles - 1) / tiles);
+    int64_t per = std::max<int64_t>(64, (S + sl - 1) / sl);
+    per = (per + TS - 1) / TS * TS;
+    const int64_t slices = (S + per - 1) / per;
+    hipLaunchKernelGGL((lr::k_loo_fill<T, P>), dim3((unsigned)tiles, (unsigned)slices), dim3(lr::kLooBlock), 0, st, static_cast<const T*>(a->m->d_rows), a->n,
+                       static_cast<const T*>(d_draws), S, per, static_cast<T*>(a->d_ll), a->ld, a->S);
+    LR_HIP(hipGetLastError());
+    a->S += S;
+    return LR_OK;
+}
+int loo_fill_any(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
+    const lr_model* m = a->m;
+    switch (m->P) {  // every padded width the library has, both dtypes
+#define LR_LOO_CASE(W) \
+    case W: return m->dtype == LR_F32 ? loo_fill<float, W>(a, d_draws, S, st) : loo_fill<double, W>(a, d_draws, S, st);
+        LR_LOO_CASE(4) LR_LOO_CASE(8) LR_LOO_CASE(16) LR_LOO_CASE(32) LR_LOO_CASE(64) LR_LOO_CASE(128)
+#undef LR_LOO_CASE
+    }
+    return fail(LR_ERR_UNSUPPORTED, "lr_loo: unsupported padded width %d", m->P);
+}
+
+// src [A][lds] -> dst [B][ldd] on the device
+template <typename T>
+int loo_transpose(const void* src, int64_t A, int64_t B, int64_t lds, void* dst, int64_t ldd, hipStream_t st) {
+    hipLaunchKernelGGL(lr::k_loo_transpose<T>, dim3((unsigned)((A + 31) / 32), (unsigned)((B + 31) / 32)), dim3(32, 8), 0, st, static_cast<const T*>(src), A, B, lds,
+                       static_cast<T*>(dst), ldd);
+    LR_HIP(hipGetLastError());
+    return LR_OK;
+}
+
+// the PSIS stage over d_ll [r][ld] (S draws a row) -> d_table [LR_LOO_ROWS][r]; 0 < S <= LR_LOO_MAX_DRAWS
+template <typename T>
+int loo_psis(const void* d_ll, int64_t ld, int64_t S, int64_t r, double* d_table, hipStream_t st) {
+    const int M = (int)lr::loo_tail_len(S);
+    if (S <= lr::kLooSmallDraws)
+        hipLaunchKernelGGL((lr::k_psis<T, 256, 1024, 1024>), dim3((unsigned)r), dim3(256), 0, st, static_cast<const T*>(d_ll), ld, (int)S, M, r, d_table);
+    else
+        hipLaunchKernelGGL((lr::k_psis<T, 512, 4096, 3072>), dim3((unsigned)r), dim3(512), 0, st, static_cast<const T*>(d_ll), ld, (int)S, M, r, d_table);
+    LR_HIP(hipGetLastError());
+    return LR_OK;
+}
+}  // namespace
+extern "C" {
+
+int lr_loo_create(lr_model* m, int64_t max_draws, lr_loo** out) {
+    if (!m || !out) return fail(LR_ERR_INVALID, "lr_loo_create: model / out is NULL");
+    if (max_draws <= 0) return fail(LR_ERR_INVALID, "lr_loo_create: max_draws must be positive (got %lld)", (long long)max_draws);
+    if (max_draws > LR_LOO_MAX_DRAWS)
+        return fail(LR_ERR_UNSUPPORTED, "lr_loo_create: max_draws = %lld is beyond LR_LOO_MAX_DRAWS = %d (the tail of an observation is sorted in on-chip memory)",
+                    (long long)max_draws, LR_LOO_MAX_DRAWS);
+    if (m->n > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_loo_create: n = %lld is beyond the launch grid", (long long)m->n);
+    LR_HIP(hipSetDevice(m->device));
+    lr_loo* a = new lr_loo();
+    a->m = m;
+    a->device = m->device;
+    a->n = m->n;
+    a->dtype = m->dtype;
+    a->es = m->esize();
+    a->cap = max_draws;
+    const int64_t line = lr::kLooTileBytes / (int64_t)a->es;
+    a->ld = (max_draws + line - 1) / line * line;
+    const size_t want = (size_t)a->n * a->ld * a->es;
+    if (hipMalloc(&a->d_ll, want) != hipSuccess) {
+        lr_loo_destroy(a);
+        return fail(LR_ERR_NOMEM, "lr_loo_create: allocating %zu bytes for the log-likelihood of %lld rows x %lld draws failed", want, (long long)m->n, (long long)max_draws);
+    }
+    if (hipMalloc((void**)&a->d_table, (size_t)LR_LOO_ROWS * a->n * sizeof(double)) != hipSuccess) {
+        lr_loo_destroy(a);
+        return fail(LR_ERR_NOMEM, "lr_loo_create: allocating the table failed");
+    }
+    *out = a;
+    return LR_OK;
+}
+
+int lr_loo_accumulate(lr_loo* a, const void* draws, int64_t S, int32_t on_device, void* stream) {
+    if (!a || !draws) return fail(LR_ERR_INVALID, "lr_loo_accumulate: accumulator / draws is NULL");
+    if (S <= 0) return fail(LR_ERR_INVALID, "lr_loo_accumulate: S must be positive (got %lld)", (long long)S);
+    if (S > a->cap - a->S)
+        return fail(LR_ERR_INVALID, "lr_loo_accumulate: %lld draws held + %lld more exceed max_draws = %lld", (long long)a->S, (long long)S, (long long)a->cap);
+    lr_model* m = a->m;
+    LR_HIP(hipSetDevice(a->device));
+    hipStream_t st = (hipStream_t)stream;
+    a->last = st;
+    const size_t es = a->es, in_row = (size_t)m->p * es, k_row = (size_t)m->P * es;
+    const bool pad = m->p != m->P;
+    // pieces of at most 256 MB of kernel-width draws, every workspace sized for the largest (the first) before anything is enqueued
+    const int64_t piece = std::max<int64_t>(1024, (int64_t)((size_t(256) << 20) / k_row));
+    const int64_t S0 = std::min(piece, S);
+    if (!on_device)
+        if (const int rc = loo_grow(&a->d_in, &a->in_bytes, (size_t)S0 * in_row, "staged draws")) return rc;
+    if (pad)
+        if (const int rc = loo_grow(&a->d_pad, &a->pad_bytes, (size_t)S0 * k_row, "padded draws")) return rc;
+    for (int64_t s0 = 0; s0 < S; s0 += piece) {
+        const int64_t Sb = std::min(piece, S - s0);
+        const void* src = static_cast<const unsigned char*>(draws) + (size_t)s0 * in_row;
+        if (!on_device) {
+            LR_HIP(hipMemcpyAsync(a->d_in, src, (size_t)Sb * in_row, hipMemcpyHostToDevice, st));
+            src = a->d_in;
+        }
+        if (pad) {
+            const unsigned blocks = (unsigned)(((size_t)Sb * m->P + 255) / 256);
+            if (m->dtype == LR_F32)
+                hipLaunchKernelGGL(lr::k_predict_pad<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(src), Sb, m->p, m->P, static_cast<float*>(a->d_pad));
+            else
+                hipLaunchKernelGGL(lr::k_predict_pad<double>, dim3(blocks), dim3(256), 0, st, static_cast<const double*>(src), Sb, m->p, m->P, static_cast<double*>(a->d_pad));
+            LR_HIP(hipGetLastError());
+            src = a->d_pad;
+        }
+        if (const int rc = loo_fill_any(a, src, Sb, st)) return rc;
+        if (!on_device && s0 + piece < S) LR_HIP(hipStreamSynchronize(st));  // the staging buffer is about to be overwritten
+    }
+    if (!on_device) LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_loo_loglik(lr_loo* a, void* host_out, int64_t* n_draws) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_loo_loglik: accumulator is NULL");
+    if (n_draws) *n_draws = a->S;
+    if (!host_out || a->S == 0) return LR_OK;
+    LR_HIP(hipSetDevice(a->device));
+    const size_t bytes = (size_t)a->S * a->n * a->es;
+    if (const int rc = loo_grow(&a->d_out, &a->out_bytes, bytes, "the transposed matrix")) return rc;
+    if (const int rc = a->dtype == LR_F32 ? loo_transpose<float>(a->d_ll, a->n, a->S, a->ld, a->d_out, a->n, a->last)
+                                          : loo_transpose<double>(a->d_ll, a->n, a->S, a->ld, a->d_out, a->n, a->last))
+        return rc;
+    LR_HIP(hipMemcpyAsync(host_out, a->d_out, bytes, hipMemcpyDeviceToHost, a->last));
+    LR_HIP(hipStreamSynchronize(a->last));
+    return LR_OK;
+}
+
+int lr_loo_result(lr_loo* a, double* table, int64_t* n_draws) {
+    if (!a || !table) return fail(LR_ERR_INVALID, "lr_loo_result: accumulator / table is NULL");
+    if (n_draws) *n_draws = a->S;
+    const size_t cells = (size_t)LR_LOO_ROWS * a->n;
+    if (a->S == 0) {
+        for (size_t e = 0; e < cells; ++e) table[e] = NAN;
+        return LR_OK;
+    }
+    LR_HIP(hipSetDevice(a->device));
+    if (const int rc = a->dtype == LR_F32 ? loo_psis<float>(a->d_ll, a->ld, a->S, a->n, a->d_table, a->last) : loo_psis<double>(a->d_ll, a->ld, a->S, a->n, a->d_table, a->last))
+        return rc;
+    LR_HIP(hipMemcpyAsync(table, a->d_table, cells * sizeof(double), hipMemcpyDeviceToHost, a->last));
+    LR_HIP(hipStreamSynchronize(a->last));
+    return LR_OK;
+}
+
+int lr_loo_reset(lr_loo* a) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_loo_reset: accumulator is NULL");
+    a->S = 0;  // the next draws overwrite the matrix from its first column
+    return LR_OK;
+}
+
+void lr_loo_destroy(lr_loo* a) {
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    for (void* q : {a->d_ll, (void*)a->d_table, a->d_in, a->d_pad, a->d_out})
+        if (q) (void)hipFree(q);
+    delete a;
+}
+
+int lr_psis(int device, const void* loglik, int64_t S, int64_t r, int32_t dtype, int32_t on_device, double* table, void* stream) {
+    if (!loglik || !table) return fail(LR_ERR_INVALID, "lr_psis: loglik / table is NULL");
+    if (S <= 0 || r <= 0) return fail(LR_ERR_INVALID, "lr_psis: S and r must be positive (got %lld, %lld)", (long long)S, (long long)r);
+    if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_psis: dtype must be LR_F32 or LR_F64");
+    if (S > LR_LOO_MAX_DRAWS)
+        return fail(LR_ERR_UNSUPPORTED, "lr_psis: S = %lld is beyond LR_LOO_MAX_DRAWS = %d (the tail of an observation is sorted in on-chip memory)", (long long)S,
+                    LR_LOO_MAX_DRAWS);
+    if (r > 65535ll * 32) return fail(LR_ERR_UNSUPPORTED, "lr_psis: r = %lld is beyond the launch grid", (long long)r);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
+    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_psis: device %d not available (%d visible)", device, ndev);
+    LR_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = dtype == LR_F32 ? 4 : 8;
+    const int64_t line = lr::kLooTileBytes / (int64_t)es, ld = (S + line - 1) / line * line;
+    DevBuf din, dt, dtab;
+    if ((!on_device && din.alloc((size_t)S * r * es)) || dt.alloc((size_t)r * ld * es) || dtab.alloc((size_t)LR_LOO_ROWS * r * sizeof(double)))
+        return fail(LR_ERR_NOMEM, "lr_psis: allocating the workspaces of a %lld x %lld matrix failed", (long long)S, (long long)r);
+    const void* src = loglik;
+    if (!on_device) {
+        LR_HIP(hipMemcpyAsync(din.p, loglik, (size_t)S * r * es, hipMemcpyHostToDevice, st));
+        src = din.p;
+    }
+    int rc = dtype == LR_F32 ? loo_transpose<float>(src, S, r, r, dt.p, ld, st) : loo_transpose<double>(src, S, r, r, dt.p, ld, st);
+    if (!rc) rc = dtype == LR_F32 ? loo_psis<float>(dt.p, ld, S, r, static_cast<double*>(dtab.p), st) : loo_psis<double>(dt.p, ld, S, r, static_cast<double*>(dtab.p), st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);  // the workspaces are freed on return
+        return rc;
+    }
+    LR_HIP(hipMemcpyAsync(table, dtab.p, (size_t)LR_LOO_ROWS * r * sizeof(double), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
 }
 
 // ---- device memory / stream / event helpers -------------------------------------------------------

@@ -603,7 +603,7 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
-         autocorr=None, marginals=None, predictive=None):
+         autocorr=None, loo=None, marginals=None, predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -639,6 +639,10 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     `"marginals": marginals.result()` (min/max, mean, variance, skewness, kurtosis, the histograms; `quantile`, `interval` and `hpd` of
     logreg_amd.marginals read quantiles and credible intervals off it).  Chains, states, statistics and accept counts are those of the
     same call without it.
+    `loo` (fused kernels): a `PsisLoo` of the kernel's own model with `max_draws` >= the draws it already holds + iters x chains.  Every
+    chunk's block of kept samples is appended to its log-likelihood matrix on the device where `predictive` is fed; the summary dict --
+    or, with `return_info=True`, the info dict -- gains `"loo": loo.result()` (elpd_loo, p_loo, se, looic, the Pareto k-hat per
+    observation).  Chains, states, statistics and accept counts are those of the same call without it.
     `plan_chains`, `plan_first`: chain count to plan the kernel variant for and the global id of that run's first chain (a shard of
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
@@ -649,6 +653,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             raise ValueError("autocorr= needs a fused kernel (the closures of a LogReg)")
         if marginals is not None:
             raise ValueError("marginals= needs a fused kernel (the closures of a LogReg)")
+        if loo is not None:
+            raise ValueError("loo= needs a fused kernel (the closures of a LogReg)")
         return _mcmc_generic(init, kernel, thin, iters, verb)
     if predictive is not None and getattr(predictive, "model", None) is not kernel.model:
         raise ValueError("predictive= must be a PosteriorPredictive of the kernel's own model")
@@ -672,6 +678,16 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         if (marginals.chains, marginals.p, marginals.dtype, marginals.device) != want:
             raise ValueError(f"marginals= is for {marginals.chains} chains x p={marginals.p} of {marginals.dtype.name} on device {marginals.device}; "
                              f"this run has {want[0]} chains x p={want[1]} of {want[2].name} on device {want[3]}")
+    if loo is not None:  # refused before anything runs
+        from .loo import PsisLoo
+        km = kernel.model
+        if not isinstance(loo, PsisLoo):
+            raise ValueError(f"loo= must be a PsisLoo; got {type(loo).__name__}")
+        if loo.model is not km:
+            raise ValueError("loo= must be a PsisLoo of the kernel's own model (its rows, dtype and device)")
+        need = loo.n_draws + int(iters) * int(np.atleast_2d(init).shape[0])
+        if need > loo.max_draws:
+            raise ValueError(f"loo= has max_draws = {loo.max_draws}; this run brings its draws to {need}")
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
     cs = ChainSet(kernel, init, seed, chain_offset=chain_offset, ll=ll, group=group, mode=mode, precision=precision,
@@ -695,7 +711,7 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         done = 0
         while done < iters:
             k = min(chunk, iters - done)
-            if predictive is None and autocorr is None and marginals is None:
+            if predictive is None and autocorr is None and marginals is None and loo is None:
                 cs.advance(k, thin, keep=False)
                 cs.sync()
             else:  # the chunk's samples exist on the device just long enough to be folded into the accumulator(s)
@@ -704,6 +720,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
                     autocorr.update(out, stream=cs.stream)
                 if marginals is not None:
                     marginals.update(out, stream=cs.stream)
+                if loo is not None:
+                    loo.update(out, stream=cs.stream)
                 if predictive is not None:
                     predictive.update(out, stream=cs.stream)
                 cs.sync()
@@ -725,6 +743,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             res["autocorr"] = autocorr.result()
         if marginals is not None:
             res["marginals"] = marginals.result()
+        if loo is not None:
+            res["loo"] = loo.result()
         if predictive is not None:
             res["predictive"] = predictive
         return res
@@ -739,6 +759,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             autocorr.update(out, stream=cs.stream)
         if marginals is not None:
             marginals.update(out, stream=cs.stream)
+        if loo is not None:
+            loo.update(out, stream=cs.stream)
         if predictive is not None:
             predictive.update(out, stream=cs.stream)
         cs.sync()
@@ -763,6 +785,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
             info["autocorr"] = autocorr.result()
         if marginals is not None:
             info["marginals"] = marginals.result()
+        if loo is not None:
+            info["loo"] = loo.result()
         return res, info
     return res
 
