@@ -152,17 +152,22 @@ _marg = None
 _loo = None
 
 
+def _bind(L, table, slot=None):
+    """`L` (a loaded library handle) with the entry points of `table` bound; resolved once per handle, which the module global named
+    `slot` remembers (no slot: resolved at every call)."""
+    if slot is None or globals()[slot] is not L:
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
+            fn.restype = res
+            fn.argtypes = args
+        if slot is not None:
+            globals()[slot] = L
+    return L
+
+
 def bind_nuts(L):
     """`L` (a loaded library handle) with the NUTS entry points bound; resolved once per handle."""
-    global _nuts
-    if _nuts is L:
-        return L
-    for name, (res, args) in NUTS_SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
-    _nuts = L
-    return L
+    return _bind(L, NUTS_SYMBOLS, "_nuts")
 
 
 def load_nuts():
@@ -172,15 +177,7 @@ def load_nuts():
 
 def bind_predict(L):
     """`L` (a loaded library handle) with the prediction entry points bound; resolved once per handle."""
-    global _predict
-    if _predict is L:
-        return L
-    for name, (res, args) in PREDICT_SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
-    _predict = L
-    return L
+    return _bind(L, PREDICT_SYMBOLS, "_predict")
 
 
 def load_predict():
@@ -190,15 +187,7 @@ def load_predict():
 
 def bind_acf(L):
     """`L` (a loaded library handle) with the autocorrelation entry points bound; resolved once per handle."""
-    global _acf
-    if _acf is L:
-        return L
-    for name, (res, args) in ACF_SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
-    _acf = L
-    return L
+    return _bind(L, ACF_SYMBOLS, "_acf")
 
 
 def load_acf():
@@ -208,15 +197,7 @@ def load_acf():
 
 def bind_marginals(L):
     """`L` (a loaded library handle) with the marginals entry points bound; resolved once per handle."""
-    global _marg
-    if _marg is L:
-        return L
-    for name, (res, args) in MARG_SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
-    _marg = L
-    return L
+    return _bind(L, MARG_SYMBOLS, "_marg")
 
 
 def load_marginals():
@@ -226,15 +207,7 @@ def load_marginals():
 
 def bind_loo(L):
     """`L` (a loaded library handle) with the PSIS-LOO entry points bound; resolved once per handle."""
-    global _loo
-    if _loo is L:
-        return L
-    for name, (res, args) in LOO_SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
-    _loo = L
-    return L
+    return _bind(L, LOO_SYMBOLS, "_loo")
 
 
 def load_loo():
@@ -268,10 +241,7 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as e:
         raise LogregHipError(f"cannot load {LIB_PATH}: {e}. There is no CPU fallback.") from e
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError if the ABI and the binding drift apart
-        fn.restype = res
-        fn.argtypes = args
+    _bind(L, SYMBOLS)  # (_lib remembers the handle only once the checks below have passed)
     have, want = L.lr_build_id().decode(), _build.source_hash()
     if have != want:
         raise LogregHipError(f"{LIB_PATH} was built from other sources (build id {have}, sources {want}); "

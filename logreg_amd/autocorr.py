@@ -23,9 +23,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from ._accum import BlockAccumulator
 from ._lib import ACF_HEAD_ROWS, ACF_MAX_LAG, check
-from .model import _DTYPES, DeviceArray
 
 
 def geyer_tau(rho, n: int) -> float:
@@ -75,76 +74,19 @@ def merge_autocorr(results) -> dict:
     return result_from_sums(sums, np.concatenate([r["ess_chain"] for r in results], axis=0), n, sum(r["chains"] for r in results))
 
 
-class Autocorr:
+class Autocorr(BlockAccumulator):
     """Streaming accumulator of the lag-0..max_lag autocovariance and Geyer ESS of `chains` x `p` series of `dtype` draws on `device`.
     The device state (about 8 (3 max_lag + 3) bytes per series) is allocated at the first `update`."""
+    _prefix, _bind, _keyword = "lr_acf", "bind_acf", "autocorr"
+    _entry_points = "autocorrelation entry points (include/logreg_hip_acf.h)"
 
     def __init__(self, chains: int, p: int, dtype="float32", max_lag: int = 63, device: int = 0):
-        self._h = None
-        self._L = None
-        self._freed = False
-        key = dtype
-        if not (isinstance(dtype, str) and dtype in _DTYPES):
-            try:
-                key = np.dtype(dtype).name
-            except TypeError:
-                key = None
-        if key not in _DTYPES:
-            raise ValueError(f"dtype must be float32 or float64; got {dtype!r}")
-        self.lr_dtype, self.np_dtype = _DTYPES[key]
-        self.chains, self.p, self.max_lag, self.device = int(chains), int(p), int(max_lag), int(device)
-        if self.chains <= 0 or self.p <= 0:
-            raise ValueError(f"chains and p must be positive; got {chains}, {p}")
+        super().__init__(chains, p, dtype, device, max_lag=max_lag)
         if not 1 <= self.max_lag <= ACF_MAX_LAG or self.max_lag % 2 == 0:
             raise ValueError(f"max_lag must be odd and in 1..{ACF_MAX_LAG} (lags 0..max_lag are (max_lag + 1) / 2 Geyer pairs); got {max_lag}")
-        self.n_draws = 0
 
-    @property
-    def dtype(self):
-        return np.dtype(self.np_dtype)
-
-    @property
-    def handle(self):
-        if self._freed:
-            raise _lib.LogregHipError("accumulator was freed")
-        if self._h is None:
-            L = _lib.load()
-            _lib.require_gpu()  # no CPU path
-            try:
-                L = _lib.bind_acf(L)
-            except AttributeError as e:
-                raise _lib.LogregHipError(f"this library has no autocorrelation entry points (include/logreg_hip_acf.h): {e}") from e
-            h = C.c_void_p()
-            check(L.lr_acf_create(self.device, self.lr_dtype, self.chains, self.p, self.max_lag, C.byref(h)))
-            self._L, self._h = L, h
-        return self._h
-
-    def check_block(self, shape, dtype=None, device=None):
-        """Raise ValueError unless a block of this shape (and, for a DeviceArray, dtype and device) can be folded in."""
-        shape = tuple(shape)
-        if len(shape) != 3 or shape[1:] != (self.chains, self.p):
-            raise ValueError(f"block must be [k, C, p] with C={self.chains}, p={self.p}; got {shape}")
-        if shape[0] == 0:
-            raise ValueError("block holds no draw (k = 0)")
-        if dtype is not None and (np.dtype(dtype) != self.dtype or device != self.device):
-            raise ValueError(f"a DeviceArray block must have dtype {self.dtype.name} on device {self.device}; got {np.dtype(dtype).name} on device {device}")
-
-    def update(self, block, stream=None):
-        """Fold the next `k` time steps in: `[k, C, p]`, an ndarray (any float type; converted to the accumulator's dtype) or a
-        `DeviceArray` of its dtype (enqueued on `stream`; the array may be freed once the stream has passed).  Returns self."""
-        if isinstance(block, DeviceArray):
-            self.check_block(block.shape, block.dtype, block.device)
-            rc = _call(self, block.ptr, block.shape[0], 1, stream)
-        else:
-            block = np.asarray(block)
-            self.check_block(block.shape)
-            if block.dtype.kind not in "fiu":
-                raise ValueError(f"block must hold real numbers; got dtype {block.dtype}")
-            a = np.ascontiguousarray(block, dtype=self.np_dtype)
-            rc = _call(self, a.ctypes.data, a.shape[0], 0, stream)
-        check(rc)
-        self.n_draws += int(block.shape[0] if isinstance(block, DeviceArray) else np.shape(block)[0])
-        return self
+    def _create(self, L, out):
+        return L.lr_acf_create(self.device, self.lr_dtype, self.chains, self.p, self.max_lag, out)
 
     def sums(self):
         """(table `[max_lag + 4, p]`, per-chain ESS `[C, p]`), float64; NaN everywhere before the first draw."""
@@ -163,27 +105,5 @@ class Autocorr:
         sums, ess = self.sums()
         return result_from_sums(sums, ess, self.n_draws, self.chains)
 
-    def reset(self):
-        if self._h is not None:
-            check(self._L.lr_acf_reset(self._h))
-        self.n_draws = 0
-
-    def free(self):
-        if getattr(self, "_h", None) is not None:
-            self._L.lr_acf_destroy(self._h)
-            self._h = None
-        self._freed = True
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
     def __repr__(self):
         return f"Autocorr(chains={self.chains}, p={self.p}, dtype={self.dtype.name}, max_lag={self.max_lag}, n_draws={self.n_draws})"
-
-
-def _call(ac: Autocorr, ptr, k: int, on_device: int, stream):
-    h = ac.handle
-    return ac._L.lr_acf_accumulate(h, ptr, int(k), on_device, stream)

@@ -39,6 +39,7 @@
 
 #include "lr_plan.h"
 #include "lr_engine.h"
+#include "lr_accum.h"
 
 namespace {
 
@@ -677,7 +678,7 @@ int lr_stats_reduce(int device, const double* stats, int64_t n_chains, int32_t p
 
 // ---- posterior prediction, pointwise log-likelihood (include/logreg_hip_predict.h; kernels: lr_predict.h) ----------------------------
 }  // extern "C"
-struct lr_predict {
+struct lr_predict : Staged {
     lr_model* m = nullptr;
     int device = 0;                 // the model's (kept here: lr_predict_destroy must not need the model)
     int64_t r = 0;
@@ -687,24 +688,10 @@ struct lr_predict {
     signed char* d_sign = nullptr;  // [r] 2 y - 1 (labels only)
     double* d_acc = nullptr;        // [LR_PRED_ROWS][r] the running table
     int64_t n = 0;                  // draws folded in
-    hipStream_t last = nullptr;     // stream of the last accumulate call
-    // grow-only workspaces: slice partials, host draws staged on the device, draws padded to the kernel width
-    void* d_part = nullptr;  size_t part_bytes = 0;
-    void* d_in = nullptr;    size_t in_bytes = 0;
-    void* d_pad = nullptr;   size_t pad_bytes = 0;
+    Workspace part;                 // slice partials
 };
 namespace {
 static_assert(LR_PRED_ROWS == lr::kPredRows, "table rows");
-
-int pred_grow(void** p, size_t* have, size_t want, const char* what) {
-    if (*have >= want) return LR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_predict: allocating %zu bytes of %s failed", want, what);
-    *have = want;
-    return LR_OK;
-}
 
 // slices of one launch over S draws: enough workgroups for four waves on every SIMD, at least 64 draws each
 int64_t pred_most_slices(const lr_predict* pp, int64_t S) {  // non-decreasing in S
@@ -727,31 +714,25 @@ int pred_launch(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) 
     pred_slicing(pp, S, &per, &slices);
     const int64_t tiles = (pp->r + lr::kPredBlock - 1) / lr::kPredBlock;
     const size_t want = (size_t)slices * lr::kPredRows * pp->r * sizeof(double);
-    if (const int rc = pred_grow(&pp->d_part, &pp->part_bytes, want, "slice partials")) return rc;
+    if (const int rc = pp->part.grow(want, "lr_predict", "slice partials")) return rc;
     const dim3 grid((unsigned)tiles, (unsigned)slices);
     if (pp->labels)
         hipLaunchKernelGGL((lr::k_predict_partial<T, P, true>), grid, dim3(lr::kPredBlock), 0, st, static_cast<const T*>(pp->d_rows), pp->d_sign, pp->r,
-                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->d_part));
+                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->part.p));
     else
         hipLaunchKernelGGL((lr::k_predict_partial<T, P, false>), grid, dim3(lr::kPredBlock), 0, st, static_cast<const T*>(pp->d_rows), pp->d_sign, pp->r,
-                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->d_part));
+                           static_cast<const T*>(d_draws), S, per, static_cast<double*>(pp->part.p));
     LR_HIP(hipGetLastError());
     hipLaunchKernelGGL(lr::k_predict_merge, dim3((unsigned)((pp->r + lr::kPredMergeRows - 1) / lr::kPredMergeRows)),
-                       dim3(lr::kPredMergeRows, lr::kPredMergeWays), 0, st, static_cast<const double*>(pp->d_part), slices, per, S, pp->r, (double)pp->n,
+                       dim3(lr::kPredMergeRows, lr::kPredMergeWays), 0, st, static_cast<const double*>(pp->part.p), slices, per, S, pp->r, (double)pp->n,
                        pp->d_acc);
     LR_HIP(hipGetLastError());
     pp->n += S;
     return LR_OK;
 }
 int pred_launch_any(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) {
-    const lr_model* m = pp->m;
-    switch (m->P) {  // every padded width the library has, both dtypes
-#define LR_PRED_CASE(W) \
-    case W: return m->dtype == LR_F32 ? pred_launch<float, W>(pp, d_draws, S, st) : pred_launch<double, W>(pp, d_draws, S, st);
-        LR_PRED_CASE(4) LR_PRED_CASE(8) LR_PRED_CASE(16) LR_PRED_CASE(32) LR_PRED_CASE(64) LR_PRED_CASE(128)
-#undef LR_PRED_CASE
-    }
-    return fail(LR_ERR_UNSUPPORTED, "lr_predict: unsupported padded width %d", m->P);
+    LR_RETURN_BY_DTYPE_WIDTH(pp->m->dtype, pp->m->P, pred_launch, pp, d_draws, S, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_predict: unsupported padded width %d", pp->m->P);
 }
 }  // namespace
 extern "C" {
@@ -819,43 +800,11 @@ int lr_predict_create(lr_model* m, const double* X_new, const double* y_new, int
 int lr_predict_accumulate(lr_predict* pp, const void* draws, int64_t S, int32_t on_device, void* stream) {
     if (!pp || !draws) return fail(LR_ERR_INVALID, "lr_predict_accumulate: accumulator / draws is NULL");
     if (S <= 0) return fail(LR_ERR_INVALID, "lr_predict_accumulate: S must be positive (got %lld)", (long long)S);
-    lr_model* m = pp->m;
     LR_HIP(hipSetDevice(pp->device));
-    hipStream_t st = (hipStream_t)stream;
-    pp->last = st;
-    const size_t es = m->esize(), in_row = (size_t)m->p * es, k_row = (size_t)m->P * es;
-    const bool pad = m->p != m->P;
-    // pieces of at most 256 MB of kernel-width draws: bounds the staging buffers; the grid's y extent stays far below its limit
-    const int64_t piece = std::max<int64_t>(1024, (int64_t)((size_t(256) << 20) / k_row));
-    // every workspace at the size of the largest (the first) piece before anything is folded in: running out of memory leaves the
-    // accumulator as it was
-    const int64_t S0 = std::min(piece, S);
-    if (!on_device)
-        if (const int rc = pred_grow(&pp->d_in, &pp->in_bytes, (size_t)S0 * in_row, "staged draws")) return rc;
-    if (pad)
-        if (const int rc = pred_grow(&pp->d_pad, &pp->pad_bytes, (size_t)S0 * k_row, "padded draws")) return rc;
-    if (const int rc = pred_grow(&pp->d_part, &pp->part_bytes, (size_t)pred_most_slices(pp, S0) * lr::kPredRows * pp->r * sizeof(double), "slice partials"))
-        return rc;
-    for (int64_t s0 = 0; s0 < S; s0 += piece) {
-        const int64_t Sb = std::min(piece, S - s0);
-        const void* src = static_cast<const unsigned char*>(draws) + (size_t)s0 * in_row;
-        if (!on_device) {
-            LR_HIP(hipMemcpyAsync(pp->d_in, src, (size_t)Sb * in_row, hipMemcpyHostToDevice, st));
-            src = pp->d_in;
-        }
-        if (pad) {
-            const unsigned blocks = (unsigned)(((size_t)Sb * m->P + 255) / 256);
-            if (m->dtype == LR_F32)
-                hipLaunchKernelGGL(lr::k_predict_pad<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(src), Sb, m->p, m->P, static_cast<float*>(pp->d_pad));
-            else
-                hipLaunchKernelGGL(lr::k_predict_pad<double>, dim3(blocks), dim3(256), 0, st, static_cast<const double*>(src), Sb, m->p, m->P, static_cast<double*>(pp->d_pad));
-            LR_HIP(hipGetLastError());
-            src = pp->d_pad;
-        }
-        if (const int rc = pred_launch_any(pp, src, Sb, st)) return rc;
-    }
-    if (!on_device) LR_HIP(hipStreamSynchronize(st));
-    return LR_OK;
+    return stage_draws(
+        "lr_predict", *pp, pp->m, Feed{draws, S, on_device != 0, (hipStream_t)stream},
+        [pp](int64_t S0) { return pp->part.grow((size_t)pred_most_slices(pp, S0) * lr::kPredRows * pp->r * sizeof(double), "lr_predict", "slice partials"); },
+        [pp](const void* d_draws, int64_t Sb, hipStream_t st) { return pred_launch_any(pp, d_draws, Sb, st); });
 }
 
 int lr_predict_result(lr_predict* pp, double* table, int64_t* n_draws) {
@@ -866,7 +815,8 @@ int lr_predict_result(lr_predict* pp, double* table, int64_t* n_draws) {
         LR_HIP(hipMemcpyAsync(table, pp->d_acc, cells * sizeof(double), hipMemcpyDeviceToHost, pp->last));
         LR_HIP(hipStreamSynchronize(pp->last));
     }
-    for (size_t e = pp->n > 0 ? (pp->labels ? cells : 2 * (size_t)pp->r) : 0; e < cells; ++e) table[e] = NAN;
+    const size_t held = pp->n > 0 ? (pp->labels ? cells : 2 * (size_t)pp->r) : 0;  // (without labels: the two probability rows)
+    fill_nan(table + held, cells - held);
     if (n_draws) *n_draws = pp->n;
     return LR_OK;
 }
@@ -881,25 +831,21 @@ void lr_predict_destroy(lr_predict* pp) {
     if (!pp) return;
     (void)hipSetDevice(pp->device);
     if (pp->own_rows && pp->d_rows) (void)hipFree(pp->d_rows);
-    for (void* q : {(void*)pp->d_sign, (void*)pp->d_acc, pp->d_part, pp->d_in, pp->d_pad})
-        if (q) (void)hipFree(q);
+    free_all({pp->d_sign, pp->d_acc, pp->part.p, pp->in.p, pp->padded.p});
     delete pp;
 }
 
 // ---- autocorrelation and Geyer ESS of the kept draws (include/logreg_hip_acf.h; kernels: lr_acf.h) ------------------------------------
 }  // extern "C"
-struct lr_acf {
+struct lr_acf : Staged {
     int device = 0;
     int dtype = LR_F32;
     int64_t C = 0, NS = 0;  // chains, series = C p
     int p = 0, K = 0;
     int64_t n = 0;               // time steps folded in
-    hipStream_t last = nullptr;  // stream of the last accumulate call
     double* d_state = nullptr;   // S [NS][K+1] | head [NS][K] | tail [NS][K] | total [NS] | x0 [NS]
     size_t state_bytes = 0;
-    // grow-only workspaces: host blocks staged on the device; V, the workgroup partials and the table of lr_acf_result
-    void* d_in = nullptr;  size_t in_bytes = 0;
-    void* d_ws = nullptr;  size_t ws_bytes = 0;
+    Workspace ws;                // V, the workgroup partials and the table of lr_acf_result
     size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
     double* S() const { return d_state; }
     double* head() const { return d_state + (size_t)NS * (K + 1); }
@@ -910,16 +856,6 @@ struct lr_acf {
 namespace {
 static_assert(LR_ACF_MAX_LAG == lr::kAcfMaxLag, "largest lag");
 static_assert(LR_ACF_ROWS(0) == lr::kAcfHeadRows + 1, "table rows");
-
-int acf_grow(void** p, size_t* have, size_t want, const char* what) {
-    if (*have >= want) return LR_OK;
-    void* q = nullptr;
-    if (hipMalloc(&q, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_acf: allocating %zu bytes of %s failed", want, what);
-    if (*p) (void)hipFree(*p);  // (hipFree waits for the work that still reads it)
-    *p = q;
-    *have = want;
-    return LR_OK;
-}
 
 template <typename T>
 int acf_launch(lr_acf* a, const void* d_block, int64_t k, hipStream_t st) {
@@ -946,10 +882,7 @@ int lr_acf_create(int device, int32_t dtype, int64_t C, int32_t p, int32_t max_l
         return fail(LR_ERR_INVALID, "lr_acf_create: max_lag must be odd and in 1..%d (got %d)", LR_ACF_MAX_LAG, max_lag);
     if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_acf_create: dtype must be LR_F32 or LR_F64");
     if (C > (0x7FFFFFFFll * lr::kAcfTile) / p) return fail(LR_ERR_UNSUPPORTED, "lr_acf_create: %lld x %d series are beyond the launch grid", (long long)C, p);
-    int ndev = 0;
-    LR_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_acf_create: device %d not available (%d visible)", device, ndev);
-    LR_HIP(hipSetDevice(device));
+    if (const int rc = use_device(device, "lr_acf_create")) return rc;
     lr_acf* a = new lr_acf();
     a->device = device;
     a->dtype = dtype;
@@ -977,24 +910,8 @@ int lr_acf_accumulate(lr_acf* a, const void* block, int64_t k, int32_t on_device
     if (!a || !block) return fail(LR_ERR_INVALID, "lr_acf_accumulate: accumulator / block is NULL");
     if (k <= 0) return fail(LR_ERR_INVALID, "lr_acf_accumulate: k must be positive (got %lld)", (long long)k);
     LR_HIP(hipSetDevice(a->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t row = (size_t)a->NS * a->esize();
-    // host blocks go through a staging buffer in pieces of at most 256 MB, sized before anything is folded in
-    const int64_t piece = on_device ? k : std::max<int64_t>(1, (int64_t)((size_t(256) << 20) / row));
-    if (!on_device)
-        if (const int rc = acf_grow(&a->d_in, &a->in_bytes, (size_t)std::min(piece, k) * row, "staged draws")) return rc;
-    a->last = st;
-    for (int64_t t0 = 0; t0 < k; t0 += piece) {
-        const int64_t kb = std::min(piece, k - t0);
-        const void* src = static_cast<const unsigned char*>(block) + (size_t)t0 * row;
-        if (!on_device) {
-            LR_HIP(hipMemcpyAsync(a->d_in, src, (size_t)kb * row, hipMemcpyHostToDevice, st));
-            src = a->d_in;
-        }
-        if (const int rc = a->dtype == LR_F32 ? acf_launch<float>(a, src, kb, st) : acf_launch<double>(a, src, kb, st)) return rc;
-    }
-    if (!on_device) LR_HIP(hipStreamSynchronize(st));
-    return LR_OK;
+    return stage_block("lr_acf", *a, (size_t)a->NS * a->esize(), Feed{block, k, on_device != 0, (hipStream_t)stream},
+                       [a](const void* d_block, int64_t kb, hipStream_t st) { return LR_BY_DTYPE(a->dtype, acf_launch, a, d_block, kb, st); });
 }
 
 int lr_acf_result(lr_acf* a, double* sums, double* ess_chain, int64_t* n_draws) {
@@ -1003,14 +920,13 @@ int lr_acf_result(lr_acf* a, double* sums, double* ess_chain, int64_t* n_draws) 
     const int64_t rows = LR_ACF_ROWS(a->K), cells = rows * a->p, nblocks = (a->C + 255) / 256;
     if (n_draws) *n_draws = a->n;
     if (a->n == 0) {
-        for (int64_t e = 0; e < cells; ++e) sums[e] = NAN;
-        if (ess_chain)
-            for (int64_t e = 0; e < a->NS; ++e) ess_chain[e] = NAN;
+        fill_nan(sums, (size_t)cells);
+        if (ess_chain) fill_nan(ess_chain, (size_t)a->NS);
         return LR_OK;
     }
     const size_t v_doubles = (size_t)rows * a->NS, part_doubles = (size_t)nblocks * cells;
-    if (const int rc = acf_grow(&a->d_ws, &a->ws_bytes, (v_doubles + part_doubles + (size_t)cells) * sizeof(double), "result workspace")) return rc;
-    double* V = static_cast<double*>(a->d_ws);
+    if (const int rc = a->ws.grow((v_doubles + part_doubles + (size_t)cells) * sizeof(double), "lr_acf", "result workspace")) return rc;
+    double* V = static_cast<double*>(a->ws.p);
     double* part = V + v_doubles;
     double* d_sums = part + part_doubles;
     hipStream_t st = a->last;
@@ -1038,24 +954,20 @@ int lr_acf_reset(lr_acf* a) {
 void lr_acf_destroy(lr_acf* a) {
     if (!a) return;
     (void)hipSetDevice(a->device);
-    for (void* q : {(void*)a->d_state, a->d_in, a->d_ws})
-        if (q) (void)hipFree(q);
+    free_all({a->d_state, a->in.p, a->ws.p});
     delete a;
 }
 
 // ---- marginal histograms, min / max and power sums of the kept draws (include/logreg_hip_marginals.h; kernels: lr_marginals.h) ---------
 }  // extern "C"
-struct lr_marg {
+struct lr_marg : Staged {
     int device = 0;
     int dtype = LR_F32;
     int64_t C = 0, NS = 0;  // chains, series = C p
     int p = 0, bins = 0, pt = 0;  // pt: coordinates per LDS table (= p: the flat lane map)
     int64_t n = 0;               // time steps folded in
-    hipStream_t last = nullptr;  // stream of the last accumulate call
     unsigned long long* d_state = nullptr;  // counts [p][bins+3] | sums [NS][4] | mn [NS] | mx [NS] | grid [5][p], 8 bytes each
-    // grow-only workspaces: host blocks staged on the device; the workgroup partials and the table of lr_marg_result
-    void* d_in = nullptr;  size_t in_bytes = 0;
-    void* d_ws = nullptr;  size_t ws_bytes = 0;
+    Workspace ws;                // the workgroup partials and the table of lr_marg_result
     size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
     int64_t cells() const { return (int64_t)p * LR_MARG_COLS(bins); }
     unsigned long long* counts() const { return d_state; }
@@ -1070,16 +982,6 @@ static_assert(LR_MARG_MAX_BINS == lr::kMargMaxBins, "most bins");
 static_assert(LR_MARG_ROWS == lr::kMargRows, "table rows");
 static_assert(sizeof(unsigned long long) == sizeof(uint64_t) && sizeof(double) == 8, "one state word is 8 bytes");
 static_assert((size_t)lr::kMargBlock * lr::kMargMaxSteps < (size_t(1) << 32), "an LDS counter cannot wrap within a launch");
-
-int marg_grow(void** p, size_t* have, size_t want, const char* what) {
-    if (*have >= want) return LR_OK;
-    void* q = nullptr;
-    if (hipMalloc(&q, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_marg: allocating %zu bytes of %s failed", want, what);
-    if (*p) (void)hipFree(*p);  // (hipFree waits for the work that still reads it)
-    *p = q;
-    *have = want;
-    return LR_OK;
-}
 
 int marg_clear(lr_marg* m, hipStream_t st) {
     const int64_t most = std::max(m->cells(), m->NS);
@@ -1125,10 +1027,7 @@ int lr_marg_create(int device, int32_t dtype, int64_t C, int32_t p, int32_t bins
     const int64_t per = pt == p ? 1 : lr::kMargBlock / pt, ntile = pt == p ? 1 : (p + pt - 1) / pt;
     if (C > 0x7FFFFFFFll * lr::kMargBlock / p || (C + per - 1) / per > 0x7FFFFFFFll / ntile)
         return fail(LR_ERR_UNSUPPORTED, "lr_marg_create: %lld x %d series are beyond the launch grid", (long long)C, p);
-    int ndev = 0;
-    LR_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_marg_create: device %d not available (%d visible)", device, ndev);
-    LR_HIP(hipSetDevice(device));
+    if (const int rc = use_device(device, "lr_marg_create")) return rc;
     lr_marg* m = new lr_marg();
     m->device = device;
     m->dtype = dtype;
@@ -1163,24 +1062,8 @@ int lr_marg_accumulate(lr_marg* m, const void* block, int64_t k, int32_t on_devi
     if (!m || !block) return fail(LR_ERR_INVALID, "lr_marg_accumulate: accumulator / block is NULL");
     if (k <= 0) return fail(LR_ERR_INVALID, "lr_marg_accumulate: k must be positive (got %lld)", (long long)k);
     LR_HIP(hipSetDevice(m->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t row = (size_t)m->NS * m->esize();
-    // host blocks go through a staging buffer in pieces of at most 256 MB, sized before anything is folded in
-    const int64_t piece = on_device ? k : std::max<int64_t>(1, (int64_t)((size_t(256) << 20) / row));
-    if (!on_device)
-        if (const int rc = marg_grow(&m->d_in, &m->in_bytes, (size_t)std::min(piece, k) * row, "staged draws")) return rc;
-    m->last = st;
-    for (int64_t t0 = 0; t0 < k; t0 += piece) {
-        const int64_t kb = std::min(piece, k - t0);
-        const void* src = static_cast<const unsigned char*>(block) + (size_t)t0 * row;
-        if (!on_device) {
-            LR_HIP(hipMemcpyAsync(m->d_in, src, (size_t)kb * row, hipMemcpyHostToDevice, st));
-            src = m->d_in;
-        }
-        if (const int rc = m->dtype == LR_F32 ? marg_launch<float>(m, src, kb, st) : marg_launch<double>(m, src, kb, st)) return rc;
-    }
-    if (!on_device) LR_HIP(hipStreamSynchronize(st));
-    return LR_OK;
+    return stage_block("lr_marg", *m, (size_t)m->NS * m->esize(), Feed{block, k, on_device != 0, (hipStream_t)stream},
+                       [m](const void* d_block, int64_t kb, hipStream_t st) { return LR_BY_DTYPE(m->dtype, marg_launch, m, d_block, kb, st); });
 }
 
 int lr_marg_result(lr_marg* m, uint64_t* counts, double* table, int64_t* n_draws) {
@@ -1190,14 +1073,13 @@ int lr_marg_result(lr_marg* m, uint64_t* counts, double* table, int64_t* n_draws
     if (n_draws) *n_draws = m->n;
     if (m->n == 0) {
         if (counts) std::fill(counts, counts + m->cells(), uint64_t(0));
-        if (table)
-            for (int64_t e = 0; e < tcells; ++e) table[e] = NAN;
+        if (table) fill_nan(table, (size_t)tcells);
         return LR_OK;
     }
     hipStream_t st = m->last;
     if (table) {
-        if (const int rc = marg_grow(&m->d_ws, &m->ws_bytes, (size_t)(nblocks + 1) * tcells * sizeof(double), "result workspace")) return rc;
-        double* part = static_cast<double*>(m->d_ws);
+        if (const int rc = m->ws.grow((size_t)(nblocks + 1) * tcells * sizeof(double), "lr_marg", "result workspace")) return rc;
+        double* part = static_cast<double*>(m->ws.p);
         double* d_table = part + (size_t)nblocks * tcells;
         hipLaunchKernelGGL(lr::k_marg_partial, dim3((unsigned)nblocks, (unsigned)LR_MARG_ROWS), dim3(256), 0, st, m->sums(), m->mn(), m->mx(), m->C, m->p, part);
         LR_HIP(hipGetLastError());
@@ -1222,14 +1104,13 @@ int lr_marg_reset(lr_marg* m) {
 void lr_marg_destroy(lr_marg* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    for (void* q : {(void*)m->d_state, m->d_in, m->d_ws})
-        if (q) (void)hipFree(q);
+    free_all({m->d_state, m->in.p, m->ws.p});
     delete m;
 }
 
 // ---- PSIS-LOO: the pointwise log-likelihood matrix and its Pareto-smoothed leave-one-out summary (include/logreg_hip_loo.h; kernels: lr_loo.h)
 }  // extern "C"
-struct lr_loo {
+struct lr_loo : Staged {
     lr_model* m = nullptr;
     int device = 0;              // the model's (kept here: lr_loo_destroy must not need the model)
     int64_t n = 0;               // the model's rows
@@ -1239,24 +1120,10 @@ struct lr_loo {
     void* d_ll = nullptr;        // [n][ld]
     double* d_table = nullptr;   // [LR_LOO_ROWS][n]
     int64_t S = 0;               // draws held
-    hipStream_t last = nullptr;  // stream of the last accumulate call
-    // grow-only workspaces: host draws staged on the device, draws padded to the kernel width, the matrix transposed for lr_loo_loglik
-    void* d_in = nullptr;    size_t in_bytes = 0;
-    void* d_pad = nullptr;   size_t pad_bytes = 0;
-    void* d_out = nullptr;   size_t out_bytes = 0;
+    Workspace out;               // the matrix transposed for lr_loo_loglik
 };
 namespace {
 static_assert(LR_LOO_ROWS == lr::kLooRows && LR_LOO_MAX_DRAWS == lr::kLooMaxDraws, "logreg_hip_loo.h and lr_loo.h");
-
-int loo_grow(void** p, size_t* have, size_t want, const char* what) {
-    if (*have >= want) return LR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_loo: allocating %zu bytes of %s failed", want, what);
-    *have = want;
-    return LR_OK;
-}
 
 template <typename T, int P>
 int loo_fill(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
@@ -1274,14 +1141,8 @@ int loo_fill(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
     return LR_OK;
 }
 int loo_fill_any(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
-    const lr_model* m = a->m;
-    switch (m->P) {  // every padded width the library has, both dtypes
-#define LR_LOO_CASE(W) \
-    case W: return m->dtype == LR_F32 ? loo_fill<float, W>(a, d_draws, S, st) : loo_fill<double, W>(a, d_draws, S, st);
-        LR_LOO_CASE(4) LR_LOO_CASE(8) LR_LOO_CASE(16) LR_LOO_CASE(32) LR_LOO_CASE(64) LR_LOO_CASE(128)
-#undef LR_LOO_CASE
-    }
-    return fail(LR_ERR_UNSUPPORTED, "lr_loo: unsupported padded width %d", m->P);
+    LR_RETURN_BY_DTYPE_WIDTH(a->m->dtype, a->m->P, loo_fill, a, d_draws, S, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_loo: unsupported padded width %d", a->m->P);
 }
 
 // src [A][lds] -> dst [B][ldd] on the device
@@ -1342,40 +1203,10 @@ int lr_loo_accumulate(lr_loo* a, const void* draws, int64_t S, int32_t on_device
     if (S <= 0) return fail(LR_ERR_INVALID, "lr_loo_accumulate: S must be positive (got %lld)", (long long)S);
     if (S > a->cap - a->S)
         return fail(LR_ERR_INVALID, "lr_loo_accumulate: %lld draws held + %lld more exceed max_draws = %lld", (long long)a->S, (long long)S, (long long)a->cap);
-    lr_model* m = a->m;
     LR_HIP(hipSetDevice(a->device));
-    hipStream_t st = (hipStream_t)stream;
-    a->last = st;
-    const size_t es = a->es, in_row = (size_t)m->p * es, k_row = (size_t)m->P * es;
-    const bool pad = m->p != m->P;
-    // pieces of at most 256 MB of kernel-width draws, every workspace sized for the largest (the first) before anything is enqueued
-    const int64_t piece = std::max<int64_t>(1024, (int64_t)((size_t(256) << 20) / k_row));
-    const int64_t S0 = std::min(piece, S);
-    if (!on_device)
-        if (const int rc = loo_grow(&a->d_in, &a->in_bytes, (size_t)S0 * in_row, "staged draws")) return rc;
-    if (pad)
-        if (const int rc = loo_grow(&a->d_pad, &a->pad_bytes, (size_t)S0 * k_row, "padded draws")) return rc;
-    for (int64_t s0 = 0; s0 < S; s0 += piece) {
-        const int64_t Sb = std::min(piece, S - s0);
-        const void* src = static_cast<const unsigned char*>(draws) + (size_t)s0 * in_row;
-        if (!on_device) {
-            LR_HIP(hipMemcpyAsync(a->d_in, src, (size_t)Sb * in_row, hipMemcpyHostToDevice, st));
-            src = a->d_in;
-        }
-        if (pad) {
-            const unsigned blocks = (unsigned)(((size_t)Sb * m->P + 255) / 256);
-            if (m->dtype == LR_F32)
-                hipLaunchKernelGGL(lr::k_predict_pad<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(src), Sb, m->p, m->P, static_cast<float*>(a->d_pad));
-            else
-                hipLaunchKernelGGL(lr::k_predict_pad<double>, dim3(blocks), dim3(256), 0, st, static_cast<const double*>(src), Sb, m->p, m->P, static_cast<double*>(a->d_pad));
-            LR_HIP(hipGetLastError());
-            src = a->d_pad;
-        }
-        if (const int rc = loo_fill_any(a, src, Sb, st)) return rc;
-        if (!on_device && s0 + piece < S) LR_HIP(hipStreamSynchronize(st));  // the staging buffer is about to be overwritten
-    }
-    if (!on_device) LR_HIP(hipStreamSynchronize(st));
-    return LR_OK;
+    return stage_draws(
+        "lr_loo", *a, a->m, Feed{draws, S, on_device != 0, (hipStream_t)stream}, [](int64_t) { return LR_OK; },
+        [a](const void* d_draws, int64_t Sb, hipStream_t st) { return loo_fill_any(a, d_draws, Sb, st); });
 }
 
 int lr_loo_loglik(lr_loo* a, void* host_out, int64_t* n_draws) {
@@ -1384,11 +1215,9 @@ int lr_loo_loglik(lr_loo* a, void* host_out, int64_t* n_draws) {
     if (!host_out || a->S == 0) return LR_OK;
     LR_HIP(hipSetDevice(a->device));
     const size_t bytes = (size_t)a->S * a->n * a->es;
-    if (const int rc = loo_grow(&a->d_out, &a->out_bytes, bytes, "the transposed matrix")) return rc;
-    if (const int rc = a->dtype == LR_F32 ? loo_transpose<float>(a->d_ll, a->n, a->S, a->ld, a->d_out, a->n, a->last)
-                                          : loo_transpose<double>(a->d_ll, a->n, a->S, a->ld, a->d_out, a->n, a->last))
-        return rc;
-    LR_HIP(hipMemcpyAsync(host_out, a->d_out, bytes, hipMemcpyDeviceToHost, a->last));
+    if (const int rc = a->out.grow(bytes, "lr_loo", "the transposed matrix")) return rc;
+    if (const int rc = LR_BY_DTYPE(a->dtype, loo_transpose, a->d_ll, a->n, a->S, a->ld, a->out.p, a->n, a->last)) return rc;
+    LR_HIP(hipMemcpyAsync(host_out, a->out.p, bytes, hipMemcpyDeviceToHost, a->last));
     LR_HIP(hipStreamSynchronize(a->last));
     return LR_OK;
 }
@@ -1398,12 +1227,11 @@ int lr_loo_result(lr_loo* a, double* table, int64_t* n_draws) {
     if (n_draws) *n_draws = a->S;
     const size_t cells = (size_t)LR_LOO_ROWS * a->n;
     if (a->S == 0) {
-        for (size_t e = 0; e < cells; ++e) table[e] = NAN;
+        fill_nan(table, cells);
         return LR_OK;
     }
     LR_HIP(hipSetDevice(a->device));
-    if (const int rc = a->dtype == LR_F32 ? loo_psis<float>(a->d_ll, a->ld, a->S, a->n, a->d_table, a->last) : loo_psis<double>(a->d_ll, a->ld, a->S, a->n, a->d_table, a->last))
-        return rc;
+    if (const int rc = LR_BY_DTYPE(a->dtype, loo_psis, a->d_ll, a->ld, a->S, a->n, a->d_table, a->last)) return rc;
     LR_HIP(hipMemcpyAsync(table, a->d_table, cells * sizeof(double), hipMemcpyDeviceToHost, a->last));
     LR_HIP(hipStreamSynchronize(a->last));
     return LR_OK;
@@ -1418,8 +1246,7 @@ int lr_loo_reset(lr_loo* a) {
 void lr_loo_destroy(lr_loo* a) {
     if (!a) return;
     (void)hipSetDevice(a->device);
-    for (void* q : {a->d_ll, (void*)a->d_table, a->d_in, a->d_pad, a->d_out})
-        if (q) (void)hipFree(q);
+    free_all({a->d_ll, a->d_table, a->in.p, a->padded.p, a->out.p});
     delete a;
 }
 
@@ -1431,10 +1258,7 @@ int lr_psis(int device, const void* loglik, int64_t S, int64_t r, int32_t dtype,
         return fail(LR_ERR_UNSUPPORTED, "lr_psis: S = %lld is beyond LR_LOO_MAX_DRAWS = %d (the tail of an observation is sorted in on-chip memory)", (long long)S,
                     LR_LOO_MAX_DRAWS);
     if (r > 65535ll * 32) return fail(LR_ERR_UNSUPPORTED, "lr_psis: r = %lld is beyond the launch grid", (long long)r);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
-    if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "lr_psis: device %d not available (%d visible)", device, ndev);
-    LR_HIP(hipSetDevice(device));
+    if (const int rc = use_device(device, "lr_psis", true)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t es = dtype == LR_F32 ? 4 : 8;
     const int64_t line = lr::kLooTileBytes / (int64_t)es, ld = (S + line - 1) / line * line;
@@ -1446,8 +1270,8 @@ int lr_psis(int device, const void* loglik, int64_t S, int64_t r, int32_t dtype,
         LR_HIP(hipMemcpyAsync(din.p, loglik, (size_t)S * r * es, hipMemcpyHostToDevice, st));
         src = din.p;
     }
-    int rc = dtype == LR_F32 ? loo_transpose<float>(src, S, r, r, dt.p, ld, st) : loo_transpose<double>(src, S, r, r, dt.p, ld, st);
-    if (!rc) rc = dtype == LR_F32 ? loo_psis<float>(dt.p, ld, S, r, static_cast<double*>(dtab.p), st) : loo_psis<double>(dt.p, ld, S, r, static_cast<double*>(dtab.p), st);
+    int rc = LR_BY_DTYPE(dtype, loo_transpose, src, S, r, r, dt.p, ld, st);
+    if (!rc) rc = LR_BY_DTYPE(dtype, loo_psis, dt.p, ld, S, r, static_cast<double*>(dtab.p), st);
     if (rc) {
         (void)hipStreamSynchronize(st);  // the workspaces are freed on return
         return rc;

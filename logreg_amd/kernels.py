@@ -601,6 +601,18 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
     return int(max(1, min(iters, 2_000_000_000 // work_per_kept)))
 
 
+def _accumulator_class(keyword):
+    """(class, its name with an article) of the accumulator `mcmc` takes as `keyword=`"""
+    if keyword == "autocorr":
+        from .autocorr import Autocorr
+        return Autocorr, "an Autocorr"
+    if keyword == "marginals":
+        from .marginals import Marginals
+        return Marginals, "a Marginals"
+    from .loo import PsisLoo
+    return PsisLoo, "a PsisLoo"
+
+
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
          autocorr=None, loo=None, marginals=None, predictive=None):
@@ -646,48 +658,34 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     `plan_chains`, `plan_first`: chain count to plan the kernel variant for and the global id of that run's first chain (a shard of
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
+    # the accumulators given: refused in the order of the keywords here, fed and reported in the order of `accs`
+    given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("marginals", marginals), ("loo", loo)) if acc is not None}
+    accs = [(name, given[name]) for name in ("autocorr", "marginals", "loo", "predictive") if name in given]
     if not isinstance(kernel, FusedKernel):
-        if predictive is not None:
-            raise ValueError("predictive= needs a fused kernel (the closures of a LogReg)")
-        if autocorr is not None:
-            raise ValueError("autocorr= needs a fused kernel (the closures of a LogReg)")
-        if marginals is not None:
-            raise ValueError("marginals= needs a fused kernel (the closures of a LogReg)")
-        if loo is not None:
-            raise ValueError("loo= needs a fused kernel (the closures of a LogReg)")
+        for name in given:
+            raise ValueError(f"{name}= needs a fused kernel (the closures of a LogReg)")
         return _mcmc_generic(init, kernel, thin, iters, verb)
     if predictive is not None and getattr(predictive, "model", None) is not kernel.model:
         raise ValueError("predictive= must be a PosteriorPredictive of the kernel's own model")
     init = np.asarray(init, dtype=np.float64)
     single = init.ndim == 1
-    if autocorr is not None:  # refused before anything runs
-        from .autocorr import Autocorr
-        km = kernel.model
-        if not isinstance(autocorr, Autocorr):
-            raise ValueError(f"autocorr= must be an Autocorr; got {type(autocorr).__name__}")
-        want = (int(np.atleast_2d(init).shape[0]), km.p, np.dtype(km.np_dtype), km.device)
-        if (autocorr.chains, autocorr.p, autocorr.dtype, autocorr.device) != want:
-            raise ValueError(f"autocorr= is for {autocorr.chains} chains x p={autocorr.p} of {autocorr.dtype.name} on device {autocorr.device}; "
-                             f"this run has {want[0]} chains x p={want[1]} of {want[2].name} on device {want[3]}")
-    if marginals is not None:  # refused before anything runs
-        from .marginals import Marginals
-        km = kernel.model
-        if not isinstance(marginals, Marginals):
-            raise ValueError(f"marginals= must be a Marginals; got {type(marginals).__name__}")
-        want = (int(np.atleast_2d(init).shape[0]), km.p, np.dtype(km.np_dtype), km.device)
-        if (marginals.chains, marginals.p, marginals.dtype, marginals.device) != want:
-            raise ValueError(f"marginals= is for {marginals.chains} chains x p={marginals.p} of {marginals.dtype.name} on device {marginals.device}; "
-                             f"this run has {want[0]} chains x p={want[1]} of {want[2].name} on device {want[3]}")
-    if loo is not None:  # refused before anything runs
-        from .loo import PsisLoo
-        km = kernel.model
-        if not isinstance(loo, PsisLoo):
-            raise ValueError(f"loo= must be a PsisLoo; got {type(loo).__name__}")
-        if loo.model is not km:
-            raise ValueError("loo= must be a PsisLoo of the kernel's own model (its rows, dtype and device)")
-        need = loo.n_draws + int(iters) * int(np.atleast_2d(init).shape[0])
-        if need > loo.max_draws:
-            raise ValueError(f"loo= has max_draws = {loo.max_draws}; this run brings its draws to {need}")
+    for name, acc in given.items():  # refused before anything runs
+        if name != "predictive":
+            cls, a_cls = _accumulator_class(name)
+            if not isinstance(acc, cls):
+                raise ValueError(f"{name}= must be {a_cls}; got {type(acc).__name__}")
+            acc.check_run(np.atleast_2d(init).shape[0], kernel.model, iters)
+
+    def fold(out):  # a chunk's block of kept samples, still on the device
+        for _, acc in accs:
+            acc.update(out, stream=cs.stream)
+
+    def attach(d, info=False):  # the results; predictive goes into a summary as the object itself and into no info dict
+        for name, acc in accs:
+            if name != "predictive":
+                d[name] = acc.result()
+            elif not info:
+                d[name] = acc
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
     cs = ChainSet(kernel, init, seed, chain_offset=chain_offset, ll=ll, group=group, mode=mode, precision=precision,
@@ -711,19 +709,12 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         done = 0
         while done < iters:
             k = min(chunk, iters - done)
-            if predictive is None and autocorr is None and marginals is None and loo is None:
+            if not accs:
                 cs.advance(k, thin, keep=False)
                 cs.sync()
             else:  # the chunk's samples exist on the device just long enough to be folded into the accumulator(s)
                 out = cs.advance(k, thin, keep=True)
-                if autocorr is not None:
-                    autocorr.update(out, stream=cs.stream)
-                if marginals is not None:
-                    marginals.update(out, stream=cs.stream)
-                if loo is not None:
-                    loo.update(out, stream=cs.stream)
-                if predictive is not None:
-                    predictive.update(out, stream=cs.stream)
+                fold(out)
                 cs.sync()
                 out.free()
             done += k
@@ -739,14 +730,7 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         else:
             res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)))
         res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
-        if autocorr is not None:
-            res["autocorr"] = autocorr.result()
-        if marginals is not None:
-            res["marginals"] = marginals.result()
-        if loo is not None:
-            res["loo"] = loo.result()
-        if predictive is not None:
-            res["predictive"] = predictive
+        attach(res)
         return res
     mat = np.empty((iters, cs.C, m.p), dtype=m.np_dtype)
     if verb:
@@ -755,14 +739,7 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     while done < iters:
         k = min(chunk, iters - done)
         out = cs.advance(k, thin, keep=True)
-        if autocorr is not None:
-            autocorr.update(out, stream=cs.stream)
-        if marginals is not None:
-            marginals.update(out, stream=cs.stream)
-        if loo is not None:
-            loo.update(out, stream=cs.stream)
-        if predictive is not None:
-            predictive.update(out, stream=cs.stream)
+        fold(out)
         cs.sync()
         mat[done:done + k] = out.to_host()
         out.free()
@@ -781,12 +758,7 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
                     "plan": cs.plan(), "iterations": iters * thin}
         if getattr(kernel, "proposal", None):  # RWMH: how the proposal was recognised ("rwProposal" | "probed": mhKernel)
             info["proposal"] = kernel.proposal
-        if autocorr is not None:
-            info["autocorr"] = autocorr.result()
-        if marginals is not None:
-            info["marginals"] = marginals.result()
-        if loo is not None:
-            info["loo"] = loo.result()
+        attach(info, info=True)
         return res, info
     return res
 

@@ -25,6 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._accum import ModelAccumulator
 from ._lib import LOO_MAX_DRAWS, LOO_ROWS, check
 from .model import DeviceArray, LogReg
 
@@ -76,8 +77,9 @@ def _bind(L):
         raise _lib.LogregHipError(f"the library behind this call has no PSIS-LOO entry points (include/logreg_hip_loo.h): {e}") from e
 
 
-class PsisLoo:
+class PsisLoo(ModelAccumulator):
     """Accumulator of the pointwise log-likelihood of `model`'s own rows under up to `max_draws` draws, and its PSIS-LOO summary."""
+    _prefix = "lr_loo"
 
     def __init__(self, model: LogReg, max_draws: int):
         self._h = None
@@ -99,12 +101,6 @@ class PsisLoo:
         self.n_draws = 0
 
     @property
-    def handle(self):
-        if self._h is None:
-            raise _lib.LogregHipError("accumulator was closed")
-        return self._h
-
-    @property
     def dtype(self):
         return np.dtype(self.model.np_dtype)
 
@@ -112,38 +108,22 @@ class PsisLoo:
     def device(self):
         return self.model.device
 
-    def update(self, draws, stream=None):
-        """Append draws: `[S, p]` or `[iters, C, p]`, an ndarray (any float type; converted to the model's dtype) or a `DeviceArray`
-        of the model's dtype (enqueued on `stream`; the array may be freed once the stream has passed).  More than `max_draws` in all
-        is refused and leaves the accumulator as it was.  Returns self."""
-        m = self.model
-        m.handle  # (raises if the model was closed: the accumulator reads the model's rows)
-        shape = draws.shape if isinstance(draws, DeviceArray) else np.shape(draws)
-        if len(shape) not in (2, 3) or shape[-1] != m.p:
-            raise ValueError(f"draws must be [S, p] or [iters, C, p] with p={m.p}; got {tuple(shape)}")
-        S = int(np.prod(shape[:-1], dtype=np.int64))
-        if S == 0:
-            raise ValueError("draws holds no draw (S = 0)")
+    def _check_room(self, S):
         if self.n_draws + S > self.max_draws:
             raise ValueError(f"{self.n_draws} draws held + {S} more exceed max_draws = {self.max_draws}")
-        if isinstance(draws, DeviceArray):
-            if draws.dtype != np.dtype(m.np_dtype) or draws.device != m.device:
-                raise ValueError(f"a DeviceArray of draws must have the model's dtype {np.dtype(m.np_dtype).name} and device {m.device}; "
-                                 f"got {draws.dtype.name} on device {draws.device}")
-            rc = self._L.lr_loo_accumulate(self.handle, draws.ptr, S, 1, stream)
-        else:
-            a = np.ascontiguousarray(draws, dtype=m.np_dtype)
-            rc = self._L.lr_loo_accumulate(self.handle, a.ctypes.data, S, 0, stream)
-        if rc == 0:
-            self.n_draws += S
-        else:  # a device error part-way: the library's count (the pieces it did append) is the one that holds
-            try:
-                check(rc)
-            finally:
-                n = C.c_int64()
-                if self._L.lr_loo_loglik(self.handle, None, C.byref(n)) == 0:
-                    self.n_draws = int(n.value)
-        return self
+
+    def _library_count(self):
+        n = C.c_int64()
+        return int(n.value) if self._L.lr_loo_loglik(self.handle, None, C.byref(n)) == 0 else None
+
+    def check_run(self, chains, model, iters):
+        """Raise ValueError unless this is an accumulator of `model` with room for the `iters` x `chains` draws of a run (`mcmc`, before
+        anything runs)."""
+        if self.model is not model:
+            raise ValueError("loo= must be a PsisLoo of the kernel's own model (its rows, dtype and device)")
+        need = self.n_draws + int(iters) * int(chains)
+        if need > self.max_draws:
+            raise ValueError(f"loo= has max_draws = {self.max_draws}; this run brings its draws to {need}")
 
     def loglik(self) -> np.ndarray:
         """The pointwise log-likelihood `[S, n]` in the model's dtype, in arrival order -- what arviz-style tools take."""
@@ -169,17 +149,6 @@ class PsisLoo:
     def reset(self):
         check(self._L.lr_loo_reset(self.handle))
         self.n_draws = 0
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self._L.lr_loo_destroy(self._h)  # (safe after the model was closed: the accumulator frees its own buffers only)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __repr__(self):
         return f"PsisLoo(n={self.n}, max_draws={self.max_draws}, n_draws={self.n_draws}, {self.model!r})"

@@ -25,9 +25,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from ._accum import BlockAccumulator
 from ._lib import MARG_MAX_BINS, MARG_ROWS, check
-from .model import _DTYPES, DeviceArray
 
 
 def marginal_grid(center, scale, width: float = 8.0):
@@ -189,80 +188,23 @@ def merge_marginals(results) -> dict:
     return result_from_tables(counts, table, first["lo"], first["hi"], first["n"], sum(r["chains"] for r in results))
 
 
-class Marginals:
+class Marginals(BlockAccumulator):
     """Streaming accumulator of the marginal histograms (`bins` bins on [lo_j, hi_j) per coordinate), min / max and power sums of `chains`
     x `p` series of `dtype` draws on `device`.  The device state (8 p (bins + 3) bytes of counts and 48 bytes per series) is allocated
     at the first `update`."""
+    _prefix, _bind, _keyword = "lr_marg", "bind_marginals", "marginals"
+    _entry_points = "marginals entry points (include/logreg_hip_marginals.h)"
 
     def __init__(self, chains: int, p: int, dtype="float32", lo=None, hi=None, bins: int = 256, device: int = 0):
-        self._h = None
-        self._L = None
-        self._freed = False
-        key = dtype
-        if not (isinstance(dtype, str) and dtype in _DTYPES):
-            try:
-                key = np.dtype(dtype).name
-            except TypeError:
-                key = None
-        if key not in _DTYPES:
-            raise ValueError(f"dtype must be float32 or float64; got {dtype!r}")
-        self.lr_dtype, self.np_dtype = _DTYPES[key]
-        self.chains, self.p, self.bins, self.device = int(chains), int(p), int(bins), int(device)
-        if self.chains <= 0 or self.p <= 0:
-            raise ValueError(f"chains and p must be positive; got {chains}, {p}")
+        super().__init__(chains, p, dtype, device, bins=bins)
         if not 1 <= self.bins <= MARG_MAX_BINS:
             raise ValueError(f"bins must be in 1..{MARG_MAX_BINS}; got {bins}")
         if lo is None or hi is None:
             raise ValueError("lo and hi (the grid, one pair per coordinate; see marginal_grid) are required")
         self.lo, self.hi = _grid(lo, hi, self.p)
-        self.n_draws = 0
 
-    @property
-    def dtype(self):
-        return np.dtype(self.np_dtype)
-
-    @property
-    def handle(self):
-        if self._freed:
-            raise _lib.LogregHipError("accumulator was freed")
-        if self._h is None:
-            L = _lib.load()
-            _lib.require_gpu()  # no CPU path
-            try:
-                L = _lib.bind_marginals(L)
-            except AttributeError as e:
-                raise _lib.LogregHipError(f"this library has no marginals entry points (include/logreg_hip_marginals.h): {e}") from e
-            h = C.c_void_p()
-            check(L.lr_marg_create(self.device, self.lr_dtype, self.chains, self.p, self.bins, self.lo.ctypes.data, self.hi.ctypes.data, C.byref(h)))
-            self._L, self._h = L, h
-        return self._h
-
-    def check_block(self, shape, dtype=None, device=None):
-        """Raise ValueError unless a block of this shape (and, for a DeviceArray, dtype and device) can be folded in."""
-        shape = tuple(shape)
-        if len(shape) != 3 or shape[1:] != (self.chains, self.p):
-            raise ValueError(f"block must be [k, C, p] with C={self.chains}, p={self.p}; got {shape}")
-        if shape[0] == 0:
-            raise ValueError("block holds no draw (k = 0)")
-        if dtype is not None and (np.dtype(dtype) != self.dtype or device != self.device):
-            raise ValueError(f"a DeviceArray block must have dtype {self.dtype.name} on device {self.device}; got {np.dtype(dtype).name} on device {device}")
-
-    def update(self, block, stream=None):
-        """Fold the next `k` time steps in: `[k, C, p]`, an ndarray (any float type; converted to the accumulator's dtype) or a
-        `DeviceArray` of its dtype (enqueued on `stream`; the array may be freed once the stream has passed).  Returns self."""
-        if isinstance(block, DeviceArray):
-            self.check_block(block.shape, block.dtype, block.device)
-            rc = _call(self, block.ptr, block.shape[0], 1, stream)
-        else:
-            block = np.asarray(block)
-            self.check_block(block.shape)
-            if block.dtype.kind not in "fiu":
-                raise ValueError(f"block must hold real numbers; got dtype {block.dtype}")
-            a = np.ascontiguousarray(block, dtype=self.np_dtype)
-            rc = _call(self, a.ctypes.data, a.shape[0], 0, stream)
-        check(rc)
-        self.n_draws += int(block.shape[0])
-        return self
+    def _create(self, L, out):
+        return L.lr_marg_create(self.device, self.lr_dtype, self.chains, self.p, self.bins, self.lo.ctypes.data, self.hi.ctypes.data, out)
 
     def counts_table(self):
         """(counts `[p, bins + 3]` uint64, table `[6, p]` float64); zeros and NaN before the first draw."""
@@ -281,27 +223,5 @@ class Marginals:
         counts, table = self.counts_table()
         return result_from_tables(counts, table, self.lo, self.hi, self.n_draws, self.chains)
 
-    def reset(self):
-        if self._h is not None:
-            check(self._L.lr_marg_reset(self._h))
-        self.n_draws = 0
-
-    def free(self):
-        if getattr(self, "_h", None) is not None:
-            self._L.lr_marg_destroy(self._h)
-            self._h = None
-        self._freed = True
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
     def __repr__(self):
         return f"Marginals(chains={self.chains}, p={self.p}, dtype={self.dtype.name}, bins={self.bins}, n_draws={self.n_draws})"
-
-
-def _call(mg: Marginals, ptr, k: int, on_device: int, stream):
-    h = mg.handle
-    return mg._L.lr_marg_accumulate(h, ptr, int(k), on_device, stream)

@@ -28,8 +28,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._accum import ModelAccumulator
 from ._lib import PRED_ROWS, check
-from .model import DeviceArray, LogReg
+from .model import LogReg
 
 
 def waic_from_table(table, n_draws: int) -> dict:
@@ -85,9 +86,10 @@ def merge_predictive(tables, counts):
     return acc, n
 
 
-class PosteriorPredictive:
+class PosteriorPredictive(ModelAccumulator):
     """Streaming accumulator of the posterior predictive of `model` at the rows `X_new` (None: the model's own design and labels,
     which are on the device already) with optional labels `y_new` in {0, 1}."""
+    _prefix = "lr_predict"
 
     def __init__(self, model: LogReg, X_new=None, y_new=None):
         self._h = None
@@ -128,45 +130,10 @@ class PosteriorPredictive:
         self._h = h
         self.n_draws = 0
 
-    @property
-    def handle(self):
-        if self._h is None:
-            raise _lib.LogregHipError("accumulator was closed")
-        return self._h
-
-    def update(self, draws, stream=None):
-        """Fold draws in: `[S, p]` or `[iters, C, p]`, an ndarray (any float type; converted to the model's dtype) or a `DeviceArray`
-        of the model's dtype (enqueued on `stream`; the array may be freed once the stream has passed).  Returns self."""
-        m = self.model
-        m.handle  # (raises if the model was closed: the accumulator reads the model's rows)
-        shape = draws.shape if isinstance(draws, DeviceArray) else np.shape(draws)
-        if len(shape) not in (2, 3) or shape[-1] != m.p:
-            raise ValueError(f"draws must be [S, p] or [iters, C, p] with p={m.p}; got {tuple(shape)}")
-        S = int(np.prod(shape[:-1], dtype=np.int64))
-        if S == 0:
-            raise ValueError("draws holds no draw (S = 0)")
-        if isinstance(draws, DeviceArray):
-            if draws.dtype != np.dtype(m.np_dtype) or draws.device != m.device:
-                raise ValueError(f"a DeviceArray of draws must have the model's dtype {np.dtype(m.np_dtype).name} and device {m.device}; "
-                                 f"got {draws.dtype.name} on device {draws.device}")
-            rc = self._L.lr_predict_accumulate(self.handle, draws.ptr, S, 1, stream)
-        else:
-            a = np.ascontiguousarray(draws, dtype=m.np_dtype)
-            rc = self._L.lr_predict_accumulate(self.handle, a.ctypes.data, S, 0, stream)
-        if rc == 0:
-            self.n_draws += S
-        else:  # a device error part-way: the library's count (the pieces it did fold in) is the one that holds
-            try:
-                check(rc)
-            finally:
-                self._sync_count()
-        return self
-
-    def _sync_count(self):
+    def _library_count(self):
         n = C.c_int64()
         scratch = np.empty((PRED_ROWS, self.r), dtype=np.float64)
-        if self._L.lr_predict_result(self.handle, scratch.ctypes.data, C.byref(n)) == 0:
-            self.n_draws = int(n.value)
+        return int(n.value) if self._L.lr_predict_result(self.handle, scratch.ctypes.data, C.byref(n)) == 0 else None
 
     def table(self) -> np.ndarray:
         """The table `[5, r]` (float64) of the draws so far; NaN everywhere before the first draw."""
@@ -198,17 +165,6 @@ class PosteriorPredictive:
         if not self.has_labels:
             raise ValueError("WAIC needs labels (y_new)")
         return waic_from_table(self.table(), self.n_draws)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None:
-            self._L.lr_predict_destroy(self._h)  # (safe after the model was closed: the accumulator frees its own buffers only)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __repr__(self):
         return f"PosteriorPredictive(r={self.r}, labels={self.has_labels}, n_draws={self.n_draws}, {self.model!r})"

@@ -4,15 +4,23 @@
 // number: it checks that every path of the host engine -- model images of every kind, one- and two-part plans with their fork / join
 // events, the stepwise engines and their workspaces, two chain sets on two streams, statistics, the Hessian, every error return, a
 // failing allocation at every point of model creation -- touches only memory it owns, frees what it allocates, and waits only on
-// events it recorded.
+// events it recorded.  The four accumulators of kept draws (lr_predict, lr_acf, lr_marg, lr_loo) and lr_psis go through the same: their
+// whole life from host and device buffers, input longer than one staging piece, every refused argument, a failing allocation at every
+// allocation of create, accumulate and result.
 //   engine_harness all        every scenario on one thread
 //   engine_harness threads    two host threads, one model / stream / chain set each, running concurrently (ThreadSanitizer)
 #include "logreg_hip.h"
+#include "logreg_hip_acf.h"
+#include "logreg_hip_loo.h"
+#include "logreg_hip_marginals.h"
+#include "logreg_hip_predict.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -388,6 +396,356 @@ static void scenario_second_device() {
     hipstub_set_devices(1);
 }
 
+// ---- the accumulators of kept draws -------------------------------------------------------------------------------------------------
+// One accumulator behind closures, so that one life cycle and one failing-allocation sweep serve all four.  feed takes `items` draws (of a
+// model) or time steps (of a block) from a zero-filled buffer; result makes every result call the accumulator has and reports the draws held
+// and the first cell of the table.
+struct Acc {
+    std::string name;
+    size_t item_bytes;          // one draw / one time step as the caller hands it over
+    const char* kernel;         // the kernel every staged piece launches once (marginals: once per 4096 steps of it)
+    std::function<int()> create;
+    std::function<bool()> made;
+    std::function<int(const void*, int64_t, int, void*)> feed;
+    std::function<int(int64_t*, double*)> result;
+    std::function<int()> reset;
+    std::function<void()> destroy;
+};
+
+static Acc acc_predict(lr_model* const* m, int p, int dtype, int64_t rows, bool own_rows) {
+    auto h = std::make_shared<lr_predict*>(nullptr);
+    auto X = std::make_shared<std::vector<double>>((size_t)rows * p, 0.25);
+    auto y = std::make_shared<std::vector<double>>((size_t)rows, 1.0);
+    Acc a;
+    a.name = own_rows ? "predict, the model's own rows" : "predict, new rows";
+    a.item_bytes = (size_t)p * (dtype == LR_F32 ? 4 : 8);
+    a.kernel = "k_predict_partial";
+    a.create = [=] { return lr_predict_create(*m, own_rows ? nullptr : X->data(), own_rows ? nullptr : y->data(), rows, h.get()); };
+    a.made = [=] { return *h != nullptr; };
+    a.feed = [=](const void* src, int64_t S, int on_device, void* st) { return lr_predict_accumulate(*h, src, S, on_device, st); };
+    a.result = [=](int64_t* n, double* first) {
+        std::vector<double> t((size_t)LR_PRED_ROWS * rows, 7.0);
+        const int rc = lr_predict_result(*h, t.data(), n);
+        *first = t[0];
+        return rc;
+    };
+    a.reset = [=] { return lr_predict_reset(*h); };
+    a.destroy = [=] { lr_predict_destroy(*h); *h = nullptr; };
+    return a;
+}
+static Acc acc_loo(lr_model* const* m, int p, int dtype, int64_t rows, int64_t max_draws) {
+    auto h = std::make_shared<lr_loo*>(nullptr);
+    Acc a;
+    a.name = "loo";
+    a.item_bytes = (size_t)p * (dtype == LR_F32 ? 4 : 8);
+    a.kernel = "k_loo_fill";
+    a.create = [=] { return lr_loo_create(*m, max_draws, h.get()); };
+    a.made = [=] { return *h != nullptr; };
+    a.feed = [=](const void* src, int64_t S, int on_device, void* st) { return lr_loo_accumulate(*h, src, S, on_device, st); };
+    a.result = [=](int64_t* n, double* first) {
+        std::vector<double> t((size_t)LR_LOO_ROWS * rows, 7.0);
+        int64_t held = -1;
+        int rc = lr_loo_loglik(*h, nullptr, &held);  // (the count alone)
+        std::vector<unsigned char> ll((size_t)(held > 0 ? held : 0) * rows * 8 + 1);
+        if (!rc) rc = lr_loo_loglik(*h, ll.data(), nullptr);
+        if (!rc) rc = lr_loo_result(*h, t.data(), n);
+        else *n = held;
+        *first = t[0];
+        return rc;
+    };
+    a.reset = [=] { return lr_loo_reset(*h); };
+    a.destroy = [=] { lr_loo_destroy(*h); *h = nullptr; };
+    return a;
+}
+static Acc acc_acf(int dtype, int64_t C, int p, int max_lag) {
+    auto h = std::make_shared<lr_acf*>(nullptr);
+    Acc a;
+    a.name = "acf";
+    a.item_bytes = (size_t)C * p * (dtype == LR_F32 ? 4 : 8);
+    a.kernel = "k_acf_accumulate";
+    a.create = [=] { return lr_acf_create(0, dtype, C, p, max_lag, h.get()); };
+    a.made = [=] { return *h != nullptr; };
+    a.feed = [=](const void* src, int64_t k, int on_device, void* st) { return lr_acf_accumulate(*h, src, k, on_device, st); };
+    a.result = [=](int64_t* n, double* first) {
+        std::vector<double> sums((size_t)LR_ACF_ROWS(max_lag) * p, 7.0), ess((size_t)C * p, 7.0);
+        int rc = lr_acf_result(*h, sums.data(), nullptr, n);
+        if (!rc) rc = lr_acf_result(*h, sums.data(), ess.data(), n);
+        *first = sums[0];
+        return rc;
+    };
+    a.reset = [=] { return lr_acf_reset(*h); };
+    a.destroy = [=] { lr_acf_destroy(*h); *h = nullptr; };
+    return a;
+}
+static Acc acc_marg(int dtype, int64_t C, int p, int bins) {
+    auto h = std::make_shared<lr_marg*>(nullptr);
+    auto lo = std::make_shared<std::vector<double>>((size_t)p, -1.0);
+    auto hi = std::make_shared<std::vector<double>>((size_t)p, 1.0);
+    Acc a;
+    a.name = "marginals";
+    a.item_bytes = (size_t)C * p * (dtype == LR_F32 ? 4 : 8);
+    a.kernel = "k_marg_accumulate";
+    a.create = [=] { return lr_marg_create(0, dtype, C, p, bins, lo->data(), hi->data(), h.get()); };
+    a.made = [=] { return *h != nullptr; };
+    a.feed = [=](const void* src, int64_t k, int on_device, void* st) { return lr_marg_accumulate(*h, src, k, on_device, st); };
+    a.result = [=](int64_t* n, double* first) {
+        std::vector<uint64_t> counts((size_t)p * LR_MARG_COLS(bins), 7);
+        std::vector<double> t((size_t)LR_MARG_ROWS * p, 7.0);
+        int rc = lr_marg_result(*h, counts.data(), nullptr, n);
+        if (!rc) rc = lr_marg_result(*h, nullptr, t.data(), n);
+        if (!rc) rc = lr_marg_result(*h, counts.data(), t.data(), n);
+        *first = t[0];
+        return rc;
+    };
+    a.reset = [=] { return lr_marg_reset(*h); };
+    a.destroy = [=] { lr_marg_destroy(*h); *h = nullptr; };
+    return a;
+}
+
+// create, host and device input on a stream, the result before the first draw and after, reset, more draws, destroy
+static void accumulator_life(const Acc& a, const void* zeros, void* stream) {
+    int64_t n = -1;
+    double first = 0;
+    EXPECT(a.create() == LR_OK && a.made(), "%s: create", a.name.c_str());
+    if (!a.made()) return;
+    EXPECT(a.result(&n, &first) == LR_OK && n == 0 && std::isnan(first), "%s: NaN before the first draw (n %lld, %g)", a.name.c_str(), (long long)n, first);
+    Dev dev(7 * a.item_bytes);
+    EXPECT(dev.p != nullptr, "device input");
+    const long l0 = hipstub_launches_on(stream), k0 = hipstub_launches_of(a.kernel);
+    EXPECT(a.feed(zeros, 5, 0, stream) == LR_OK, "%s: host input", a.name.c_str());
+    EXPECT(a.feed(dev.p, 7, 1, stream) == LR_OK, "%s: device input", a.name.c_str());
+    EXPECT(hipstub_launches_of(a.kernel) == k0 + 2 && hipstub_launches_on(stream) >= l0 + 2, "%s: one piece each, on the caller's stream", a.name.c_str());
+    EXPECT(a.result(&n, &first) == LR_OK && n == 12, "%s: result of 12 (n %lld)", a.name.c_str(), (long long)n);
+    EXPECT(a.reset() == LR_OK && a.result(&n, &first) == LR_OK && n == 0 && std::isnan(first), "%s: reset", a.name.c_str());
+    EXPECT(a.feed(zeros, 3, 0, nullptr) == LR_OK && a.result(&n, &first) == LR_OK && n == 3, "%s: more draws after a reset, on the NULL stream", a.name.c_str());
+    EXPECT(lr_stream_sync(0, stream) == LR_OK, "sync");
+    a.destroy();
+}
+
+// host input one item longer than one staging piece of `piece` items: two pieces in one call, as the same items in two calls cut there
+static void accumulator_two_pieces(const Acc& a, int64_t piece, const void* zeros, void* stream) {
+    int64_t n = -1;
+    double first = 0;
+    EXPECT(a.create() == LR_OK && a.made(), "%s: create", a.name.c_str());
+    if (!a.made()) return;
+    const long k0 = hipstub_launches_of(a.kernel);
+    EXPECT(a.feed(zeros, piece, 0, stream) == LR_OK && hipstub_launches_of(a.kernel) == k0 + 1, "%s: %lld items are one piece", a.name.c_str(), (long long)piece);
+    EXPECT(a.feed(zeros, 1, 0, stream) == LR_OK && hipstub_launches_of(a.kernel) == k0 + 2, "%s: one more", a.name.c_str());
+    EXPECT(a.reset() == LR_OK, "reset");
+    EXPECT(a.feed(zeros, piece + 1, 0, stream) == LR_OK && hipstub_launches_of(a.kernel) == k0 + 4, "%s: %lld items are two pieces", a.name.c_str(), (long long)piece + 1);
+    EXPECT(a.result(&n, &first) == LR_OK && n == piece + 1, "%s: all of them counted (n %lld)", a.name.c_str(), (long long)n);
+    a.destroy();
+}
+
+// the k-th device allocation fails, for every k that create, accumulate (first use and regrow) and result make: LR_ERR_NOMEM, the draw
+// count as it was, nothing leaked, the accumulator usable afterwards
+static void accumulator_failing_allocations(const Acc& a, const void* zeros) {
+    int64_t n = -1;
+    double first = 0;
+    const long live0 = hipstub_live_allocs();
+    long m0 = hipstub_mallocs();
+    EXPECT(a.create() == LR_OK && a.made(), "%s: create", a.name.c_str());
+    const long in_create = hipstub_mallocs() - m0;
+    m0 = hipstub_mallocs();
+    EXPECT(a.feed(zeros, 3, 0, nullptr) == LR_OK, "%s: feed", a.name.c_str());
+    const long in_feed = hipstub_mallocs() - m0;
+    m0 = hipstub_mallocs();
+    EXPECT(a.feed(zeros, 40, 0, nullptr) == LR_OK, "%s: a longer feed", a.name.c_str());
+    const long in_regrow = hipstub_mallocs() - m0;
+    m0 = hipstub_mallocs();
+    EXPECT(a.result(&n, &first) == LR_OK && n == 43, "%s: result", a.name.c_str());
+    const long in_result = hipstub_mallocs() - m0;
+    a.destroy();
+    EXPECT(hipstub_live_allocs() == live0, "%s: %ld device buffers outlive the accumulator", a.name.c_str(), hipstub_live_allocs() - live0);
+    EXPECT(in_create >= 1 && in_feed >= 1 && in_regrow >= 1 && in_regrow <= in_feed, "%s: allocations %ld / %ld / %ld / %ld", a.name.c_str(), in_create, in_feed, in_regrow, in_result);
+    for (long k = 1; k <= in_create; ++k) {
+        hipstub_fail_malloc_at(k);
+        const int rc = a.create();
+        hipstub_fail_malloc_at(-1);
+        EXPECT(rc == LR_ERR_NOMEM && !a.made(), "%s: allocation %ld of %ld of create fails: rc %d", a.name.c_str(), k, in_create, rc);
+        if (a.made()) a.destroy();
+        EXPECT(hipstub_live_allocs() == live0, "%s: allocation %ld of create fails: %ld device buffers leaked", a.name.c_str(), k, hipstub_live_allocs() - live0);
+    }
+    for (int regrow = 0; regrow < 2; ++regrow)
+        for (long k = 1; k <= (regrow ? in_regrow : in_feed); ++k) {  // (a workspace that is large enough does not grow again)
+            EXPECT(a.create() == LR_OK && a.made(), "%s: fresh", a.name.c_str());
+            if (regrow) EXPECT(a.feed(zeros, 3, 0, nullptr) == LR_OK, "%s: feed", a.name.c_str());
+            const int64_t before = regrow ? 3 : 0;
+            hipstub_fail_malloc_at(k);
+            const int rc = a.feed(zeros, 40, 0, nullptr);
+            hipstub_fail_malloc_at(-1);
+            EXPECT(rc == LR_ERR_NOMEM, "%s: allocation %ld of accumulate fails (regrow %d): rc %d", a.name.c_str(), k, regrow, rc);
+            EXPECT(a.result(&n, &first) == LR_OK && n == before, "%s: the count stays %lld after a failed accumulate (n %lld)", a.name.c_str(), (long long)before, (long long)n);
+            EXPECT(a.feed(zeros, 40, 0, nullptr) == LR_OK && a.result(&n, &first) == LR_OK && n == before + 40, "%s: usable after a failed accumulate", a.name.c_str());
+            a.destroy();
+            EXPECT(hipstub_live_allocs() == live0, "%s: a failed accumulate leaked %ld device buffers", a.name.c_str(), hipstub_live_allocs() - live0);
+        }
+    for (long k = 1; k <= in_result; ++k) {
+        EXPECT(a.create() == LR_OK && a.made() && a.feed(zeros, 43, 0, nullptr) == LR_OK, "%s: fresh", a.name.c_str());
+        hipstub_fail_malloc_at(k);
+        const int rc = a.result(&n, &first);
+        hipstub_fail_malloc_at(-1);
+        EXPECT(rc == LR_ERR_NOMEM && n == 43, "%s: allocation %ld of %ld of result fails: rc %d, n %lld", a.name.c_str(), k, in_result, rc, (long long)n);
+        EXPECT(a.result(&n, &first) == LR_OK && n == 43 && a.feed(zeros, 2, 0, nullptr) == LR_OK, "%s: usable after a failed result", a.name.c_str());
+        a.destroy();
+        EXPECT(hipstub_live_allocs() == live0, "%s: a failed result leaked %ld device buffers", a.name.c_str(), hipstub_live_allocs() - live0);
+    }
+}
+
+static void scenario_accumulators() {
+    // zero-filled input for everything below: 65 time steps of the 8192 x 64 float64 block (64 steps of it are one 256 MB staging piece)
+    const int64_t bigC = 8192;
+    const int bigp = 64;
+    const std::vector<unsigned char> zeros((size_t)65 * bigC * bigp * 8, 0);
+    void* stream = nullptr;
+    EXPECT(lr_stream_create(0, &stream) == LR_OK, "stream");
+    for (int dtype : {LR_F32, LR_F64}) {
+        for (int p : {8, 5}) {  // p == P, and draws padded to the kernel width
+            const Data d = make_data(16, p, 31);
+            lr_model* m = nullptr;
+            EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), dtype, 0, &m) == LR_OK, "create");
+            for (const Acc& a : {acc_predict(&m, p, dtype, d.n, true), acc_predict(&m, p, dtype, 9, false), acc_loo(&m, p, dtype, d.n, 100)}) {
+                accumulator_life(a, zeros.data(), stream);
+                accumulator_failing_allocations(a, zeros.data());
+            }
+            // the accumulators own their buffers: destroyed after the model
+            const Acc pr = acc_predict(&m, p, dtype, 9, false), lo = acc_loo(&m, p, dtype, d.n, 10);
+            EXPECT(pr.create() == LR_OK && lo.create() == LR_OK && pr.feed(zeros.data(), 4, 0, stream) == LR_OK && lo.feed(zeros.data(), 4, 0, stream) == LR_OK, "feed");
+            lr_model_destroy(m);
+            pr.destroy();
+            lo.destroy();
+        }
+        for (const Acc& a : {acc_acf(dtype, 37, 5, 3), acc_marg(dtype, 37, 5, 8)}) {
+            accumulator_life(a, zeros.data(), stream);
+            accumulator_failing_allocations(a, zeros.data());
+        }
+        // the PSIS stage alone, host and device matrix
+        std::vector<double> table((size_t)LR_LOO_ROWS * 6);
+        Dev dll((size_t)30 * 6 * 8);
+        EXPECT(lr_psis(0, zeros.data(), 30, 6, dtype, 0, table.data(), stream) == LR_OK && lr_psis(0, dll.p, 30, 6, dtype, 1, table.data(), stream) == LR_OK, "psis");
+        EXPECT(lr_psis(0, zeros.data(), 5000, 3, dtype, 0, table.data(), nullptr) == LR_OK, "psis, the kernel of long tails");
+        for (long k = 1; k <= 3; ++k) {
+            const long live0 = hipstub_live_allocs();
+            hipstub_fail_malloc_at(k);
+            const int rc = lr_psis(0, zeros.data(), 30, 6, dtype, 0, table.data(), stream);
+            hipstub_fail_malloc_at(-1);
+            EXPECT(rc == LR_ERR_NOMEM && hipstub_live_allocs() == live0, "psis: allocation %ld fails: rc %d, %ld leaked", k, rc, hipstub_live_allocs() - live0);
+        }
+    }
+    // input one item longer than one staging piece.  Blocks: 256 MB / (8192 x 64 x 8 bytes) = 64 steps.  Draws of a float64 model with p = 100
+    // (kernel width 128): 256 MB / (128 x 8 bytes) = 262144 draws
+    accumulator_two_pieces(acc_acf(LR_F64, bigC, bigp, 1), 64, zeros.data(), stream);
+    accumulator_two_pieces(acc_marg(LR_F64, bigC, bigp, 8), 64, zeros.data(), stream);
+    {
+        const Data d = make_data(16, 100, 32);
+        lr_model* m = nullptr;
+        EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), LR_F64, 0, &m) == LR_OK, "create");
+        accumulator_two_pieces(acc_predict(&m, 100, LR_F64, d.n, true), 262144, zeros.data(), stream);
+        accumulator_two_pieces(acc_loo(&m, 100, LR_F64, d.n, 2 * 262145), 262144, zeros.data(), stream);
+        lr_model_destroy(m);
+    }
+    EXPECT(lr_stream_destroy(0, stream) == LR_OK, "stream destroy");
+}
+
+// every refused argument of the accumulators, through its error return
+static void scenario_accumulator_errors() {
+    const Data d = make_data(16, 5, 33);
+    lr_model* m = nullptr;
+    EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), LR_F32, 0, &m) == LR_OK, "create");
+    std::vector<double> X((size_t)4 * d.p, 0.5), y(4, 1.0), t(4096, 0.0), lo(5, -1.0), hi(5, 1.0);
+    std::vector<float> draws((size_t)64 * d.p, 0.f);
+    int64_t n = 0;
+
+    lr_predict* pp = nullptr;
+    EXPECT(lr_predict_create(nullptr, X.data(), y.data(), 4, &pp) == LR_ERR_INVALID && lr_predict_create(m, X.data(), y.data(), 4, nullptr) == LR_ERR_INVALID, "predict: NULL model / out");
+    EXPECT(lr_predict_create(m, X.data(), y.data(), 0, &pp) == LR_ERR_INVALID, "predict: r = 0");
+    EXPECT(lr_predict_create(m, X.data(), y.data(), (int64_t)1 << 60, &pp) == LR_ERR_UNSUPPORTED, "predict: r beyond the grid");
+    EXPECT(lr_predict_create(m, nullptr, y.data(), d.n, &pp) == LR_ERR_INVALID, "predict: labels without rows");
+    EXPECT(lr_predict_create(m, nullptr, nullptr, d.n + 1, &pp) == LR_ERR_INVALID, "predict: the model's own rows, another count");
+    y[2] = 0.5;
+    EXPECT(lr_predict_create(m, X.data(), y.data(), 4, &pp) == LR_ERR_INVALID, "predict: a label that is not 0 / 1");
+    y[2] = 0.0;
+    X[7] = INFINITY;
+    EXPECT(lr_predict_create(m, X.data(), y.data(), 4, &pp) == LR_ERR_INVALID && lr_predict_create(m, X.data(), nullptr, 4, &pp) == LR_ERR_INVALID, "predict: a row that is not finite");
+    X[7] = 0.5;
+    EXPECT(pp == nullptr, "no accumulator came out of a failed create");
+    EXPECT(lr_predict_create(m, X.data(), nullptr, 4, &pp) == LR_OK, "predict: rows without labels");
+    EXPECT(lr_predict_accumulate(nullptr, draws.data(), 4, 0, nullptr) == LR_ERR_INVALID && lr_predict_accumulate(pp, nullptr, 4, 0, nullptr) == LR_ERR_INVALID, "predict: NULL accumulator / draws");
+    EXPECT(lr_predict_accumulate(pp, draws.data(), 0, 0, nullptr) == LR_ERR_INVALID && lr_predict_accumulate(pp, draws.data(), -2, 0, nullptr) == LR_ERR_INVALID, "predict: S <= 0");
+    EXPECT(lr_predict_result(nullptr, t.data(), &n) == LR_ERR_INVALID && lr_predict_result(pp, nullptr, &n) == LR_ERR_INVALID && lr_predict_reset(nullptr) == LR_ERR_INVALID, "predict: NULL result / reset");
+    EXPECT(lr_predict_accumulate(pp, draws.data(), 6, 0, nullptr) == LR_OK && lr_predict_result(pp, t.data(), nullptr) == LR_OK && std::isnan(t[2 * 4]) && !std::isnan(t[4]),
+           "predict: without labels the rows of the labels stay NaN");
+    lr_predict_destroy(pp);
+    lr_predict_destroy(nullptr);
+
+    lr_loo* lp = nullptr;
+    EXPECT(lr_loo_create(nullptr, 10, &lp) == LR_ERR_INVALID && lr_loo_create(m, 10, nullptr) == LR_ERR_INVALID, "loo: NULL model / out");
+    EXPECT(lr_loo_create(m, 0, &lp) == LR_ERR_INVALID && lr_loo_create(m, (int64_t)LR_LOO_MAX_DRAWS + 1, &lp) == LR_ERR_UNSUPPORTED && lp == nullptr, "loo: max_draws");
+    EXPECT(lr_loo_create(m, 10, &lp) == LR_OK, "loo: create");
+    EXPECT(lr_loo_accumulate(nullptr, draws.data(), 4, 0, nullptr) == LR_ERR_INVALID && lr_loo_accumulate(lp, nullptr, 4, 0, nullptr) == LR_ERR_INVALID, "loo: NULL accumulator / draws");
+    EXPECT(lr_loo_accumulate(lp, draws.data(), 0, 0, nullptr) == LR_ERR_INVALID, "loo: S = 0");
+    EXPECT(lr_loo_accumulate(lp, draws.data(), 11, 0, nullptr) == LR_ERR_INVALID, "loo: more than max_draws at once");
+    EXPECT(lr_loo_accumulate(lp, draws.data(), 6, 0, nullptr) == LR_OK && lr_loo_accumulate(lp, draws.data(), 5, 0, nullptr) == LR_ERR_INVALID, "loo: more than max_draws in all");
+    EXPECT(lr_loo_loglik(lp, nullptr, &n) == LR_OK && n == 6, "loo: a refused accumulate leaves the count (n %lld)", (long long)n);
+    EXPECT(lr_loo_loglik(nullptr, nullptr, &n) == LR_ERR_INVALID && lr_loo_result(nullptr, t.data(), &n) == LR_ERR_INVALID && lr_loo_result(lp, nullptr, &n) == LR_ERR_INVALID &&
+               lr_loo_reset(nullptr) == LR_ERR_INVALID, "loo: NULL loglik / result / reset");
+    lr_loo_destroy(lp);
+    lr_loo_destroy(nullptr);
+
+    lr_acf* ac = nullptr;
+    EXPECT(lr_acf_create(0, LR_F32, 8, 5, 3, nullptr) == LR_ERR_INVALID, "acf: NULL out");
+    EXPECT(lr_acf_create(0, LR_F32, 0, 5, 3, &ac) == LR_ERR_INVALID && lr_acf_create(0, LR_F32, 8, 0, 3, &ac) == LR_ERR_INVALID, "acf: C, p");
+    for (int lag : {0, 2, LR_ACF_MAX_LAG + 2}) EXPECT(lr_acf_create(0, LR_F32, 8, 5, lag, &ac) == LR_ERR_INVALID, "acf: max_lag %d", lag);
+    EXPECT(lr_acf_create(0, 7, 8, 5, 3, &ac) == LR_ERR_INVALID, "acf: dtype");
+    EXPECT(lr_acf_create(0, LR_F32, (int64_t)1 << 50, 5, 3, &ac) == LR_ERR_UNSUPPORTED, "acf: series beyond the grid");
+    EXPECT(lr_acf_create(5, LR_F32, 8, 5, 3, &ac) == LR_ERR_HIP && lr_acf_create(-1, LR_F32, 8, 5, 3, &ac) == LR_ERR_HIP && ac == nullptr, "acf: device ordinal");
+    EXPECT(lr_acf_create(0, LR_F32, 8, 5, 3, &ac) == LR_OK, "acf: create");
+    EXPECT(lr_acf_accumulate(nullptr, draws.data(), 2, 0, nullptr) == LR_ERR_INVALID && lr_acf_accumulate(ac, nullptr, 2, 0, nullptr) == LR_ERR_INVALID &&
+               lr_acf_accumulate(ac, draws.data(), 0, 0, nullptr) == LR_ERR_INVALID, "acf: NULL accumulator / block, k = 0");
+    EXPECT(lr_acf_result(nullptr, t.data(), nullptr, &n) == LR_ERR_INVALID && lr_acf_result(ac, nullptr, nullptr, &n) == LR_ERR_INVALID && lr_acf_reset(nullptr) == LR_ERR_INVALID,
+           "acf: NULL result / reset");
+    lr_acf_destroy(ac);
+    lr_acf_destroy(nullptr);
+    ac = nullptr;
+
+    lr_marg* mg = nullptr;
+    EXPECT(lr_marg_create(0, LR_F32, 8, 5, 16, lo.data(), hi.data(), nullptr) == LR_ERR_INVALID && lr_marg_create(0, LR_F32, 8, 5, 16, nullptr, hi.data(), &mg) == LR_ERR_INVALID &&
+               lr_marg_create(0, LR_F32, 8, 5, 16, lo.data(), nullptr, &mg) == LR_ERR_INVALID, "marginals: NULL out / lo / hi");
+    EXPECT(lr_marg_create(0, LR_F32, 0, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_INVALID && lr_marg_create(0, LR_F32, 8, -1, 16, lo.data(), hi.data(), &mg) == LR_ERR_INVALID, "marginals: C, p");
+    for (int bins : {0, LR_MARG_MAX_BINS + 1}) EXPECT(lr_marg_create(0, LR_F32, 8, 5, bins, lo.data(), hi.data(), &mg) == LR_ERR_INVALID, "marginals: bins %d", bins);
+    EXPECT(lr_marg_create(0, 7, 8, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_INVALID, "marginals: dtype");
+    for (double bad : {1.0, 2.0, (double)NAN, (double)INFINITY}) {
+        lo[3] = bad;
+        EXPECT(lr_marg_create(0, LR_F32, 8, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_INVALID, "marginals: lo = %g, hi = 1", bad);
+    }
+    lo[3] = -1.0;
+    EXPECT(lr_marg_create(0, LR_F32, (int64_t)1 << 50, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_UNSUPPORTED, "marginals: series beyond the grid");
+    EXPECT(lr_marg_create(5, LR_F32, 8, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_HIP && mg == nullptr, "marginals: device ordinal");
+    EXPECT(lr_marg_create(0, LR_F32, 8, 5, 16, lo.data(), hi.data(), &mg) == LR_OK, "marginals: create");
+    EXPECT(lr_marg_accumulate(nullptr, draws.data(), 2, 0, nullptr) == LR_ERR_INVALID && lr_marg_accumulate(mg, nullptr, 2, 0, nullptr) == LR_ERR_INVALID &&
+               lr_marg_accumulate(mg, draws.data(), -1, 0, nullptr) == LR_ERR_INVALID, "marginals: NULL accumulator / block, k < 0");
+    EXPECT(lr_marg_result(nullptr, nullptr, t.data(), &n) == LR_ERR_INVALID && lr_marg_reset(nullptr) == LR_ERR_INVALID, "marginals: NULL result / reset");
+    EXPECT(lr_marg_result(mg, nullptr, nullptr, &n) == LR_OK && n == 0, "marginals: the count alone");
+    lr_marg_destroy(mg);
+    lr_marg_destroy(nullptr);
+    mg = nullptr;
+
+    EXPECT(lr_psis(0, nullptr, 30, 4, LR_F32, 0, t.data(), nullptr) == LR_ERR_INVALID && lr_psis(0, draws.data(), 30, 4, LR_F32, 0, nullptr, nullptr) == LR_ERR_INVALID, "psis: NULL loglik / table");
+    EXPECT(lr_psis(0, draws.data(), 0, 4, LR_F32, 0, t.data(), nullptr) == LR_ERR_INVALID && lr_psis(0, draws.data(), 30, 0, LR_F32, 0, t.data(), nullptr) == LR_ERR_INVALID, "psis: S, r");
+    EXPECT(lr_psis(0, draws.data(), 30, 4, 7, 0, t.data(), nullptr) == LR_ERR_INVALID, "psis: dtype");
+    EXPECT(lr_psis(0, draws.data(), (int64_t)LR_LOO_MAX_DRAWS + 1, 4, LR_F32, 0, t.data(), nullptr) == LR_ERR_UNSUPPORTED, "psis: S beyond LR_LOO_MAX_DRAWS");
+    EXPECT(lr_psis(0, draws.data(), 30, 65535ll * 32 + 1, LR_F32, 0, t.data(), nullptr) == LR_ERR_UNSUPPORTED, "psis: r beyond the grid");
+    EXPECT(lr_psis(5, draws.data(), 30, 4, LR_F32, 0, t.data(), nullptr) == LR_ERR_HIP, "psis: device ordinal");
+    lr_model_destroy(m);
+    // without a device: the block accumulators report the failing count, lr_psis that none is visible
+    hipstub_set_devices(0);
+    EXPECT(lr_acf_create(0, LR_F32, 8, 5, 3, &ac) == LR_ERR_HIP && std::strstr(lr_last_error(), "hipGetDeviceCount") != nullptr, "acf without a device: %s", lr_last_error());
+    EXPECT(lr_marg_create(0, LR_F32, 8, 5, 16, lo.data(), hi.data(), &mg) == LR_ERR_HIP && std::strstr(lr_last_error(), "hipGetDeviceCount") != nullptr, "marginals without a device");
+    EXPECT(lr_psis(0, draws.data(), 30, 4, LR_F32, 0, t.data(), nullptr) == LR_ERR_HIP && std::strstr(lr_last_error(), "(0 visible)") != nullptr, "psis without a device: %s", lr_last_error());
+    EXPECT(ac == nullptr && mg == nullptr, "no accumulator without a device");
+    hipstub_set_devices(1);
+}
+
 static void thread_body(int id, int* fails) {
     const Data d = id == 0 ? make_data(200, 8, 21) : make_data(600, 64, 22);
     lr_model* m = nullptr;
@@ -426,6 +784,8 @@ int main(int argc, char** argv) {
         scenario_errors();
         scenario_failing_allocations();
         scenario_second_device();
+        scenario_accumulators();
+        scenario_accumulator_errors();
     }
     EXPECT(hipstub_wrong_device() == 0, "%ld uses of another device's stream / event", hipstub_wrong_device());
     EXPECT(hipstub_bad_waits() == g_deliberate_bad_waits, "%ld waits on events that were never recorded", hipstub_bad_waits() - g_deliberate_bad_waits);

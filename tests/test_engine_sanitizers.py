@@ -8,7 +8,10 @@ runtime calls the library makes, on the host heap, launches as validated no-ops.
 statistics, planned shards, the Hessian, every forced (mode, group), two chain sets on two streams + a wide model on alternating
 streams, 40 error returns, a failing device allocation at EVERY allocation of model creation and of a run (LR_ERR_NOMEM, nothing
 leaked, the model still usable), and a model, its stream, buffers and runs on device 1 of two (what a rank > 0 of the multi-GPU job does:
-not one allocation, creation or launch may happen with device 0 current, none may touch another device's stream or event).  A sanitizer report, a leak, a wait on an unrecorded event or a bad launch configuration fails the test.
+not one allocation, creation or launch may happen with device 0 current, none may touch another device's stream or event), and the four
+accumulators of kept draws with lr_psis (csrc/lr_accum.h: their whole life from host and device buffers in both dtypes, padded and not,
+host input one item longer than a staging piece, every refused argument, a failing allocation at every allocation of create,
+accumulate and result: LR_ERR_NOMEM, the count unchanged, nothing leaked, usable afterwards).  A sanitizer report, a leak, a wait on an unrecorded event or a bad launch configuration fails the test.
 (First run, round 6: found that a failed hipMalloc left HIP's sticky error for the next launch check to trip over -- lr_model.h fail().)"""
 import os
 import subprocess

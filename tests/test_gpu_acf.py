@@ -206,6 +206,27 @@ def test_mcmc_feeds_the_accumulator_without_changing_the_run(la, dtype, kind):
     model.close()
 
 
+def test_a_host_block_one_step_longer_than_a_staging_piece_gives_the_bytes_of_two_updates(la):
+    """The one path no case above reaches: a host block that does not fit one staging piece.  One `update` with a step more than a
+    piece is the launch sequence of two `update`s cut at the piece boundary, so the bytes are the same."""
+    # a host block is staged in pieces of max(1, 256 MB / (C p esize)) time steps: 256 MB / (8192 x 64 x 8 bytes) = 64 steps.  (A change of
+    # the 256 MB needs another shape here.)
+    Cn, p, piece = 8192, 64, 64
+    x = np.random.default_rng(11).standard_normal((piece + 1, Cn, p))
+    out = []
+    for cuts in ([piece + 1], [piece, 1]):
+        ac = la.Autocorr(Cn, p, "float64", max_lag=1)
+        t0 = 0
+        for k in cuts:
+            ac.update(x[t0:t0 + k])
+            t0 += k
+        assert ac.n_draws == piece + 1
+        out.append(ac.sums())
+        ac.free()
+    assert np.all(np.isfinite(out[0][0][3:])) and np.all(out[0][0][3] > 0)
+    assert out[0][0].tobytes() == out[1][0].tobytes() and out[0][1].tobytes() == out[1][1].tobytes()
+
+
 def measure():
     """Print the error / bound ratio of every case and feeding, and the largest per dtype (profiles/r11_acf.txt)."""
     import logreg_amd as la

@@ -342,6 +342,32 @@ def test_mcmc_feeds_the_accumulator_without_changing_the_run(la, dtype):
     r["model"].close()
 
 
+def test_host_draws_one_longer_than_a_staging_piece_give_the_bytes_of_two_updates(la):
+    """The one path no case above reaches: host draws that do not fit one staging piece, padded to the kernel width on the way.  One
+    `update` with a draw more than a piece is the launch sequence of two `update`s cut at the piece boundary, so the bytes are the same."""
+    # draws are staged in pieces of max(1024, 256 MB / (P esize)) draws, P the padded width: p = 100 -> P = 128, 256 MB / (128 x 8 bytes) =
+    # 262144 draws.  (A change of the 256 MB needs another shape here.)
+    p, piece = 100, 262144
+    rng = np.random.default_rng(14)
+    X = rng.standard_normal((16, p))
+    y = (rng.random(16) < 0.5).astype(np.float64)
+    B = 0.05 * rng.standard_normal((piece + 1, p))
+    model = la.LogReg(X, y, np.full(p, 2.0), dtype="float64")
+    out = []
+    for cuts in ([piece + 1], [piece, 1]):
+        acc = la.PsisLoo(model, piece + 1)
+        s0 = 0
+        for S in cuts:
+            acc.update(B[s0:s0 + S])
+            s0 += S
+        assert acc.n_draws == piece + 1
+        out.append((acc.loglik(), acc.table()))
+        acc.close()
+    model.close()
+    assert np.all(np.isfinite(out[0][0])) and np.all(out[0][0] < 0) and np.all(np.isfinite(out[0][1][[0, 2, 3, 4]]))
+    assert out[0][0].tobytes() == out[1][0].tobytes() and out[0][1].tobytes() == out[1][1].tobytes()
+
+
 def measure():
     """Print the figures of profiles/r14_loo.txt: the fill's largest deviation per dtype (kernel against the float64 reference; the
     reference's float32 mode against its float64 mode) and the PSIS stage's per row over every table this file compares."""

@@ -227,6 +227,28 @@ def test_mcmc_feeds_the_accumulator_without_changing_the_run(la, dtype, kind):
     model.close()
 
 
+def test_a_host_block_one_step_longer_than_a_staging_piece_gives_the_bytes_of_two_updates(la):
+    """The one path no case above reaches: a host block that does not fit one staging piece.  One `update` with a step more than a
+    piece is the launch sequence of two `update`s cut at the piece boundary, so the bytes are the same."""
+    # a host block is staged in pieces of max(1, 256 MB / (C p esize)) time steps: 256 MB / (8192 x 64 x 8 bytes) = 64 steps.  (A change of
+    # the 256 MB needs another shape here.)
+    Cn, p, piece = 8192, 64, 64
+    x = np.random.default_rng(12).standard_normal((piece + 1, Cn, p))
+    out = []
+    for cuts in ([piece + 1], [piece, 1]):
+        mg = la.Marginals(Cn, p, "float64", lo=np.full(p, -3.0), hi=np.full(p, 3.0), bins=8)
+        t0 = 0
+        for k in cuts:
+            mg.update(x[t0:t0 + k])
+            t0 += k
+        assert mg.n_draws == piece + 1
+        out.append(mg.counts_table())
+        mg.free()
+    counts, table = out[0]
+    assert np.all(counts.sum(axis=1) == (piece + 1) * Cn) and np.all(counts[:, 1:9] > 0) and np.all(np.isfinite(table))
+    assert counts.tobytes() == out[1][0].tobytes() and table.tobytes() == out[1][1].tobytes()
+
+
 def measure():
     """Print the error / bound ratio of every case and feeding, and the largest per dtype (profiles/r12_marginals.txt)."""
     import logreg_amd as la

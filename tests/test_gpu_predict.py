@@ -245,6 +245,32 @@ def test_rows_and_labels_are_the_models_own(la, pima, pscale, map_beta):
     model.close()
 
 
+def test_host_draws_one_longer_than_a_staging_piece_give_the_bytes_of_two_updates(la):
+    """The one path no case above reaches: host draws that do not fit one staging piece, padded to the kernel width on the way.  One
+    `update` with a draw more than a piece is the launch sequence of two `update`s cut at the piece boundary, so the bytes are the same."""
+    # draws are staged in pieces of max(1024, 256 MB / (P esize)) draws, P the padded width: p = 100 -> P = 128, 256 MB / (128 x 8 bytes) =
+    # 262144 draws.  (A change of the 256 MB needs another shape here.)
+    p, piece = 100, 262144
+    rng = np.random.default_rng(13)
+    X = rng.standard_normal((16, p))
+    y = (rng.random(16) < 0.5).astype(np.float64)
+    B = 0.05 * rng.standard_normal((piece + 1, p))
+    model = la.LogReg(X, y, np.full(p, 2.0), dtype="float64")
+    out = []
+    for cuts in ([piece + 1], [piece, 1]):
+        pp = la.PosteriorPredictive(model)
+        s0 = 0
+        for S in cuts:
+            pp.update(B[s0:s0 + S])
+            s0 += S
+        assert pp.n_draws == piece + 1
+        out.append(pp.table())
+        pp.close()
+    model.close()
+    assert np.all(np.isfinite(out[0])) and np.all((out[0][0] > 0) & (out[0][0] < 1))
+    assert out[0].tobytes() == out[1].tobytes()
+
+
 def measure():
     """Print the four figures of profiles/r9_predict.txt: per dtype, the largest deviation over the whole test set of (a) the kernel's
     table from the float64 reference and (b) the reference's float32 mode from its float64 mode (float32 inputs)."""

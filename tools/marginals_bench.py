@@ -27,33 +27,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import logreg_amd as la  # noqa: E402
 from logreg_amd import _lib  # noqa: E402
-
-
-class Events:
-    def __init__(self, L, device, stream=None):
-        self.L, self.device, self.stream = L, device, stream
-        self.a, self.b = C.c_void_p(), C.c_void_p()
-        _lib.check(L.lr_event_create(device, C.byref(self.a)))
-        _lib.check(L.lr_event_create(device, C.byref(self.b)))
-
-    def time(self, fn):
-        ms = C.c_float()
-        _lib.check(self.L.lr_event_record(self.device, self.a, self.stream))
-        fn()
-        _lib.check(self.L.lr_event_record(self.device, self.b, self.stream))
-        _lib.check(self.L.lr_event_elapsed_ms(self.device, self.a, self.b, C.byref(ms)))
-        return ms.value * 1e-3
-
-
-def repeats(timer, fn, before=None, n=10):
-    out = []
-    for i in range(n + 1):  # the first is the warm run
-        if before is not None:
-            before()
-        t = timer(fn)
-        if i:
-            out.append(t)
-    return np.array(out)
+from bench_util import Events, repeats  # noqa: E402
 
 
 def fmt(t):

@@ -18,7 +18,6 @@ Floor: the vector-issue time of the kernel's own hot loop -- its instruction mix
 v_rcp_f64 18: profiles/r3_trans_rate.txt, profiles/r6_f64_ops_rate.txt), 1024 SIMDs at 2.4 GHz.  "share" = floor / measured time: how
 much of the time the binding resource (VALU + transcendental issue) explains."""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -28,6 +27,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 import logreg_amd as la  # noqa: E402
 from logreg_amd import _lib  # noqa: E402
+from bench_util import Events, repeats_until as repeats  # noqa: E402
 
 # hot-loop instruction mix per pair: (float32 VALU, transcendental, float64 VALU, v_rcp_f64), by (dtype, padded width) -- DESIGN.md "Prediction"
 MIX = {("float32", 8): (17.2, 3, 10, 0), ("float64", 8): (16.8, 0, 72, 2), ("float32", 128): (140.6, 3, 10.1, 0)}
@@ -38,30 +38,6 @@ SIMDS, CLOCK = 1024, 2.4e9
 def floor_seconds(dtype, P, pairs):
     cyc = sum(n * c for n, c in zip(MIX[(dtype, P)], COST))
     return pairs / 64.0 * cyc / (SIMDS * CLOCK)
-
-
-class Events:
-    def __init__(self, L, device):
-        self.L, self.device = L, device
-        self.a, self.b = C.c_void_p(), C.c_void_p()
-        _lib.check(L.lr_event_create(device, C.byref(self.a)))
-        _lib.check(L.lr_event_create(device, C.byref(self.b)))
-
-    def time(self, fn):
-        ms = C.c_float()
-        _lib.check(self.L.lr_event_record(self.device, self.a, None))
-        fn()
-        _lib.check(self.L.lr_event_record(self.device, self.b, None))
-        _lib.check(self.L.lr_event_elapsed_ms(self.device, self.a, self.b, C.byref(ms)))
-        return ms.value * 1e-3
-
-
-def repeats(timer, fn, min_total=0.5, min_n=5, max_n=200):
-    fn_time = []
-    timer(fn)  # warm
-    while (sum(fn_time) < min_total or len(fn_time) < min_n) and len(fn_time) < max_n:
-        fn_time.append(timer(fn))
-    return np.array(fn_time)
 
 
 def torch_table(torch, Bt, Xt, sgn, chunk):
