@@ -15,6 +15,7 @@ kernels through the C ABI in include/logreg_hip.h.  There is no CPU fallback.
 from ._lib import LogregHipError, device_count  # noqa: F401
 from .autocorr import Autocorr, merge_autocorr  # noqa: F401
 from .marginals import Marginals, marginal_grid, merge_marginals  # noqa: F401
+from .covariance import Covariance, covariance_scaling, merge_covariance  # noqa: F401
 from .data import load_pima, load_pima_parquet, synthetic_logreg  # noqa: F401
 from .diagnostics import describe, ess_geyer, ess_per_param, ess_pooled, split_rhat, summarise  # noqa: F401
 from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKernel, nutsKernel, rwProposal,  # noqa: F401
@@ -28,5 +29,5 @@ from .output import print_summary, read_parquet, to_frame, write_parquet  # noqa
 __all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "malaKernel", "hmcKernel", "ulKernel", "nutsKernel",
            "rwProposal", "mcmc", "load_pima", "load_pima_parquet", "synthetic_logreg", "summarise", "describe",
            "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "overdispersed_init", "write_parquet",
-           "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals",
+           "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals", "Covariance", "covariance_scaling", "merge_covariance",
            "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare"]

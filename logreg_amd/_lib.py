@@ -144,12 +144,24 @@ LOO_SYMBOLS = {
     "lr_psis": (C.c_int, [C.c_int, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
 }
 
+COV_MAX_P = 128  # LR_COV_MAX_P
+# name -> (restype, argtypes); every symbol include/logreg_hip_cov.h declares.  A table of its own like MARG_SYMBOLS, bound on first use
+# (load_covariance)
+COV_SYMBOLS = {
+    "lr_cov_create": (C.c_int, [C.c_int, _i32, _i64, _i32, _vp, _vp, C.POINTER(_vp)]),
+    "lr_cov_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_cov_result": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "lr_cov_reset": (C.c_int, [_vp]),
+    "lr_cov_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _predict = None
 _acf = None
 _marg = None
 _loo = None
+_cov = None
 
 
 def _bind(L, table, slot=None):
@@ -213,6 +225,16 @@ def bind_loo(L):
 def load_loo():
     """The library with the PSIS-LOO entry points bound (the same liblogreg_hip.so as load())."""
     return bind_loo(load())
+
+
+def bind_covariance(L):
+    """`L` (a loaded library handle) with the covariance entry points bound; resolved once per handle."""
+    return _bind(L, COV_SYMBOLS, "_cov")
+
+
+def load_covariance():
+    """The library with the covariance entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_covariance(load())
 
 
 def load():

@@ -9,6 +9,7 @@
 #include "../../include/logreg_hip_acf.h"
 #include "../../include/logreg_hip_marginals.h"
 #include "../../include/logreg_hip_loo.h"
+#include "../../include/logreg_hip_cov.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -24,6 +25,7 @@
 #include "lr_inst.h"
 #include "lr_acf.h"
 #include "lr_marginals.h"
+#include "lr_cov.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
 #include "lr_hessian.h"
@@ -1106,6 +1108,176 @@ void lr_marg_destroy(lr_marg* m) {
     (void)hipSetDevice(m->device);
     free_all({m->d_state, m->in.p, m->ws.p});
     delete m;
+}
+
+// ---- second cross-moment, chain sums of the kept draws (include/logreg_hip_cov.h; kernels: lr_cov.h) ------------------------------------
+}  // extern "C"
+struct lr_cov : Staged {
+    int device = 0;
+    int dtype = LR_F32;
+    int64_t C = 0, G = 0, groups = 0;  // chains, chains per group, chain groups
+    int p = 0, P = 0;
+    int64_t n = 0;             // time steps folded in: the absolute time of the next block's first row
+    double* d_state = nullptr;  // cells [groups R][E] | chain sums [C][p] | center [p] | scale [p]
+    Workspace ws;              // the runs and the merged tables of lr_cov_result
+    size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
+    int64_t E() const { return lr::cov_entries(P); }
+    int64_t ncell() const { return groups * lr::cov_residues(P); }
+    double* cells() const { return d_state; }
+    double* chain_sums() const { return d_state + (size_t)(ncell() * E()); }
+    double* cs() const { return chain_sums() + (size_t)C * p; }
+    size_t sums_words() const { return (size_t)(ncell() * E()) + (size_t)C * p; }
+};
+namespace {
+static_assert(LR_COV_CELL_RUN == lr::kCovCellRun && LR_COV_OUTER_RUN == lr::kCovOuterRun, "runs of the result");
+template <int P>
+constexpr bool cov_header_agrees() {
+    return LR_COV_WIDTH(P) == P && LR_COV_RESIDUES(P) == lr::cov_residues(P) && LR_COV_CHUNK(P) == lr::cov_chunk(P) && LR_COV_GROUPS(P) == lr::cov_groups(P);
+}
+static_assert(cov_header_agrees<4>() && cov_header_agrees<8>() && cov_header_agrees<16>() && cov_header_agrees<32>() && cov_header_agrees<64>() &&
+                  cov_header_agrees<128>() && LR_COV_WIDTH(LR_COV_MAX_P) == 128 && LR_COV_WIDTH(5) == 8 && LR_COV_WIDTH(1) == 4,
+              "the partition the header states is the kernels'");
+
+int cov_clear(lr_cov* h, hipStream_t st) {
+    const int64_t count = (int64_t)h->sums_words();
+    hipLaunchKernelGGL(lr::k_cov_init, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, h->d_state, count);
+    LR_HIP(hipGetLastError());
+    LR_HIP(hipStreamSynchronize(st));
+    h->n = 0;
+    return LR_OK;
+}
+
+template <typename T, int P>
+int cov_launch(lr_cov* h, const void* d_block, int64_t k, hipStream_t st) {
+    hipLaunchKernelGGL((lr::k_cov_accumulate<T, P>), dim3((unsigned)h->groups), dim3(lr::kCovBlock), 0, st, static_cast<const T*>(d_block), k, h->n, h->C, h->p, h->G,
+                       h->cs(), h->cells(), h->chain_sums());
+    LR_HIP(hipGetLastError());
+    h->n += k;
+    return LR_OK;
+}
+int cov_launch_any(lr_cov* h, const void* d_block, int64_t k, hipStream_t st) {
+    LR_RETURN_BY_DTYPE_WIDTH(h->dtype, h->P, cov_launch, h, d_block, k, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_cov: unsupported padded width %d", h->P);
+}
+}  // namespace
+extern "C" {
+
+int lr_cov_create(int device, int32_t dtype, int64_t C, int32_t p, const double* center, const double* scale, lr_cov** out) {
+    if (!out || !center || !scale) return fail(LR_ERR_INVALID, "lr_cov_create: out / center / scale is NULL");
+    if (C <= 0 || p <= 0) return fail(LR_ERR_INVALID, "lr_cov_create: C and p must be positive (got %lld, %d)", (long long)C, p);
+    if (p > LR_COV_MAX_P) return fail(LR_ERR_INVALID, "lr_cov_create: p must be in 1..%d (got %d)", LR_COV_MAX_P, p);
+    if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_cov_create: dtype must be LR_F32 or LR_F64");
+    for (int j = 0; j < p; ++j)
+        if (!(std::isfinite(center[j]) && std::isfinite(scale[j]) && scale[j] > 0))
+            return fail(LR_ERR_INVALID, "lr_cov_create: coordinate %d needs a finite center and a finite scale > 0 (got %g, %g)", j, center[j], scale[j]);
+    if (C > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_cov_create: %lld chains are beyond the launch grid", (long long)C);
+    if (const int rc = use_device(device, "lr_cov_create")) return rc;
+    lr_cov* h = new lr_cov();
+    h->device = device;
+    h->dtype = dtype;
+    h->C = C;
+    h->p = p;
+    h->P = LR_COV_WIDTH(p);
+    h->G = lr::cov_group_chains(C, h->P);
+    h->groups = (C + h->G - 1) / h->G;
+    const size_t want = (h->sums_words() + 2 * (size_t)p) * sizeof(double);
+    if (hipMalloc((void**)&h->d_state, want) != hipSuccess) {
+        delete h;
+        return fail(LR_ERR_NOMEM, "lr_cov_create: allocating %zu bytes of state failed", want);
+    }
+    std::vector<double> g(2 * (size_t)p);
+    std::copy(center, center + p, g.begin());
+    std::copy(scale, scale + p, g.begin() + p);
+    hipError_t e = hipMemcpy(h->cs(), g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess || cov_clear(h, nullptr) != LR_OK) {
+        lr_cov_destroy(h);
+        return e != hipSuccess ? fail(LR_ERR_HIP, "lr_cov_create: copying center and scale failed: %s", hipGetErrorString(e)) : LR_ERR_HIP;
+    }
+    *out = h;
+    return LR_OK;
+}
+
+int lr_cov_accumulate(lr_cov* h, const void* block, int64_t k, int32_t on_device, void* stream) {
+    if (!h || !block) return fail(LR_ERR_INVALID, "lr_cov_accumulate: accumulator / block is NULL");
+    if (k <= 0) return fail(LR_ERR_INVALID, "lr_cov_accumulate: k must be positive (got %lld)", (long long)k);
+    LR_HIP(hipSetDevice(h->device));
+    return stage_block("lr_cov", *h, (size_t)h->C * h->p * h->esize(), Feed{block, k, on_device != 0, (hipStream_t)stream},
+                       [h](const void* d_block, int64_t kb, hipStream_t st) { return cov_launch_any(h, d_block, kb, st); });
+}
+
+int lr_cov_result(lr_cov* h, double* moment, double* chain_outer, double* sum, double* chain_sums, int64_t* n_draws) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_cov_result: accumulator is NULL");
+    LR_HIP(hipSetDevice(h->device));
+    const int p = h->p;
+    const size_t pp = (size_t)p * p;
+    if (n_draws) *n_draws = h->n;
+    if (h->n == 0) {
+        if (moment) fill_nan(moment, pp);
+        if (chain_outer) fill_nan(chain_outer, pp);
+        if (sum) fill_nan(sum, (size_t)p);
+        if (chain_sums) fill_nan(chain_sums, (size_t)h->C * p);
+        return LR_OK;
+    }
+    hipStream_t st = h->last;
+    const int64_t E = h->E(), ncell = h->ncell(), F = (int64_t)pp + p;
+    const int64_t mruns = (ncell + LR_COV_CELL_RUN - 1) / LR_COV_CELL_RUN, oruns = (h->C + LR_COV_OUTER_RUN - 1) / LR_COV_OUTER_RUN;
+    const bool outer = chain_outer || sum;
+    std::vector<double> tiles, full;
+    if (moment || outer) {  // workspace: moment runs [mruns][E] | merged [E] | outer runs [oruns][F] | merged [F]
+        const size_t words = (moment ? (size_t)(mruns + 1) * E : 0) + (outer ? (size_t)(oruns + 1) * F : 0);
+        if (const int rc = h->ws.grow(words * sizeof(double), "lr_cov", "result workspace")) return rc;
+        double* w = static_cast<double*>(h->ws.p);
+        if (moment) {
+            double* merged = w + (size_t)mruns * E;
+            hipLaunchKernelGGL(lr::k_cov_runs, dim3((unsigned)((E + 255) / 256), (unsigned)mruns), dim3(256), 0, st, h->cells(), ncell, E, (int64_t)LR_COV_CELL_RUN, w);
+            LR_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lr::k_cov_runs, dim3((unsigned)((E + 255) / 256), 1u), dim3(256), 0, st, w, mruns, E, mruns, merged);
+            LR_HIP(hipGetLastError());
+            tiles.resize((size_t)E);
+            LR_HIP(hipMemcpyAsync(tiles.data(), merged, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
+            w = merged + E;
+        }
+        if (outer) {
+            double* merged = w + (size_t)oruns * F;
+            hipLaunchKernelGGL(lr::k_cov_outer, dim3((unsigned)oruns, (unsigned)((F + 255) / 256)), dim3(256), 0, st, h->chain_sums(), h->C, p, w);
+            LR_HIP(hipGetLastError());
+            hipLaunchKernelGGL(lr::k_cov_runs, dim3((unsigned)((F + 255) / 256), 1u), dim3(256), 0, st, w, oruns, F, oruns, merged);
+            LR_HIP(hipGetLastError());
+            full.resize((size_t)F);
+            LR_HIP(hipMemcpyAsync(full.data(), merged, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (chain_sums) LR_HIP(hipMemcpyAsync(chain_sums, h->chain_sums(), (size_t)h->C * p * sizeof(double), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    if (moment) {  // tiles (bi <= bj, row-major) of T x T entries -> the full symmetric matrix
+        const int T = lr::cov_tile(h->P), nb = lr::cov_nb(h->P);
+        size_t tile = 0;
+        for (int bi = 0; bi < nb; ++bi)
+            for (int bj = bi; bj < nb; ++bj, ++tile)
+                for (int a = 0; a < T; ++a)
+                    for (int b = 0; b < T; ++b) {
+                        const int i = bi * T + a, j = bj * T + b;
+                        if (i <= j && j < p) moment[(size_t)i * p + j] = moment[(size_t)j * p + i] = tiles[tile * T * T + (size_t)a * T + b];
+                    }
+    }
+    if (chain_outer)
+        for (int i = 0; i < p; ++i)
+            for (int j = i; j < p; ++j) chain_outer[(size_t)i * p + j] = chain_outer[(size_t)j * p + i] = full[(size_t)i * p + j];
+    if (sum) std::copy(full.begin() + pp, full.end(), sum);
+    return LR_OK;
+}
+
+int lr_cov_reset(lr_cov* h) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_cov_reset: accumulator is NULL");
+    LR_HIP(hipSetDevice(h->device));
+    return cov_clear(h, h->last);
+}
+
+void lr_cov_destroy(lr_cov* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    free_all({h->d_state, h->in.p, h->ws.p});
+    delete h;
 }
 
 // ---- PSIS-LOO: the pointwise log-likelihood matrix and its Pareto-smoothed leave-one-out summary (include/logreg_hip_loo.h; kernels: lr_loo.h)

@@ -609,13 +609,16 @@ def _accumulator_class(keyword):
     if keyword == "marginals":
         from .marginals import Marginals
         return Marginals, "a Marginals"
+    if keyword == "covariance":
+        from .covariance import Covariance
+        return Covariance, "a Covariance"
     from .loo import PsisLoo
     return PsisLoo, "a PsisLoo"
 
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
-         autocorr=None, loo=None, marginals=None, predictive=None):
+         autocorr=None, loo=None, covariance=None, marginals=None, predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -651,6 +654,11 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     `"marginals": marginals.result()` (min/max, mean, variance, skewness, kurtosis, the histograms; `quantile`, `interval` and `hpd` of
     logreg_amd.marginals read quantiles and credible intervals off it).  Chains, states, statistics and accept counts are those of the
     same call without it.
+    `covariance` (fused kernels): a `Covariance` of the run's chain count, p, dtype and device.  Every chunk's block of kept samples is
+    folded into it on the device exactly where `marginals` is; the summary dict -- or, with `return_info=True`, the info dict -- gains
+    `"covariance": covariance.result()` (cov, cor, the within- and between-chain matrices, the multivariate R-hat; `metric` of
+    logreg_amd.covariance turns it into a diagonal `dmm` / `pre`).  Chains, states, statistics and accept counts are those of the same
+    call without it.
     `loo` (fused kernels): a `PsisLoo` of the kernel's own model with `max_draws` >= the draws it already holds + iters x chains.  Every
     chunk's block of kept samples is appended to its log-likelihood matrix on the device where `predictive` is fed; the summary dict --
     or, with `return_info=True`, the info dict -- gains `"loo": loo.result()` (elpd_loo, p_loo, se, looic, the Pareto k-hat per
@@ -659,8 +667,9 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
     # the accumulators given: refused in the order of the keywords here, fed and reported in the order of `accs`
-    given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("marginals", marginals), ("loo", loo)) if acc is not None}
-    accs = [(name, given[name]) for name in ("autocorr", "marginals", "loo", "predictive") if name in given]
+    given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("marginals", marginals), ("covariance", covariance), ("loo", loo))
+             if acc is not None}
+    accs = [(name, given[name]) for name in ("autocorr", "marginals", "covariance", "loo", "predictive") if name in given]
     if not isinstance(kernel, FusedKernel):
         for name in given:
             raise ValueError(f"{name}= needs a fused kernel (the closures of a LogReg)")
