@@ -1,7 +1,7 @@
 // lr_accum.h -- the host scaffold the accumulators of kept draws share (lr_predict, lr_acf, lr_marg, lr_loo in lr_api.hip): a grow-only
 // device workspace, the loop that cuts one accumulate call into staged pieces, and the small helpers around them.  What differs between
 // accumulators stays with each: its struct, the argument checks of its create call, its launch, result and reset functions.
-// Host code only; included by lr_api.hip alone, after lr_model.h (fail, LR_HIP, lr_model) and lr_predict.h (k_predict_pad).
+// Host code only; included by lr_api.hip alone, after lr_model.h (fail, LR_HIP, lr_model, LR_BY_DTYPE) and lr_predict.h (k_predict_pad).
 #pragma once
 
 #include <algorithm>
@@ -9,20 +9,6 @@
 #include <initializer_list>
 
 namespace {
-
-// f<float | double>(...) and f<float | double, W>(...) by an LR_F32 / LR_F64 value
-#define LR_BY_DTYPE(dtype, f, ...) ((dtype) == LR_F32 ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
-#define LR_BY_DTYPE_W(dtype, W, f, ...) ((dtype) == LR_F32 ? f<float, W>(__VA_ARGS__) : f<double, W>(__VA_ARGS__))
-// return f<float | double, P>(...) for every padded width the library has, both dtypes; falls through on any other width
-#define LR_RETURN_BY_DTYPE_WIDTH(dtype, P, f, ...)                  \
-    switch (P) {                                                    \
-        case 4: return LR_BY_DTYPE_W(dtype, 4, f, __VA_ARGS__);     \
-        case 8: return LR_BY_DTYPE_W(dtype, 8, f, __VA_ARGS__);     \
-        case 16: return LR_BY_DTYPE_W(dtype, 16, f, __VA_ARGS__);   \
-        case 32: return LR_BY_DTYPE_W(dtype, 32, f, __VA_ARGS__);   \
-        case 64: return LR_BY_DTYPE_W(dtype, 64, f, __VA_ARGS__);   \
-        case 128: return LR_BY_DTYPE_W(dtype, 128, f, __VA_ARGS__); \
-    }
 
 // Make `device` the calling thread's, refusing one that is not there.  count_may_fail: a failing hipGetDeviceCount means "none visible"
 // instead of an error of its own (lr_psis).

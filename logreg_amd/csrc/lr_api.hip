@@ -1,7 +1,14 @@
 // lr_api.hip -- the entry points of the C ABI declared in include/logreg_hip.h: argument checking, model creation (device copies
 // and operand images), the run / eval / plan calls and the device-memory helpers.  Host-side only.  The layers below it:
-//   lr_model.h   the model handle, error reporting, variant tables          lr_plan.h    which kernel variant runs a request (data)
+//   lr_model.h   the model handle, error reporting, variant tables, the dtype x width dispatch macros
+//   lr_plan.h    which kernel variant runs a request (data): PlanReq is built by plan_request*(), planned by make_plan() / plan_run()
 //   lr_engine.h  kernel argument packing, workspaces, the stepwise driver   lr_inst*.hip the launches, one unit per (dtype, width)
+//   lr_accum.h   the scaffold of the accumulators of kept draws (the second half of this file, from the `posterior prediction` divider)
+// The first half has one of each: check_opts() for the options of every call, run_request() for the front every lr_run_* shares (check,
+// plan_run(), nothing to do, device buffers or staged()), staged() for every call made with host pointers (run, NUTS, eval: allocate
+// what the call uses, copy in, launch on the NULL stream, the only hipDeviceSynchronize of the run path, copy back), and in
+// lr_model_create one cleanup (a guard over lr_model_destroy), upload() for a device array and signed_rows() for the design, both
+// shared with lr_predict_create.
 // All arithmetic of the path runs in the kernels (lr_kernels.h, lr_mfma.h, lr_tall*.h, lr_wide*.h).
 #include "../../include/logreg_hip.h"
 #include "../../include/logreg_hip_nuts.h"
@@ -20,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "lr_inst.h"
@@ -82,49 +90,73 @@ struct DevBuf {
         return hipMalloc(&p, bytes) == hipSuccess ? 0 : -1;
     }
 };
+// One array of a call made with host pointers.  host = NULL: an optional array the caller left out -- nothing is allocated or copied
+// and the launch gets NULL.
+struct HostBuf {
+    void* host;
+    size_t bytes;
+    bool in, out;  // copied to the device before the launch / back after it
+};
+// launch(d) enqueues on the NULL stream with d[i] the device copy of b[i]; the arrays come back only after a launch that worked
+template <size_t N, typename Launch>
+int staged(const HostBuf (&b)[N], Launch&& launch) {
+    DevBuf d[N];
+    void* dp[N];
+    for (size_t i = 0; i < N; ++i) {
+        if (b[i].host && d[i].alloc(b[i].bytes)) return fail(LR_ERR_NOMEM, "device allocation failed (array %zu of the call: %zu bytes)", i, b[i].bytes);
+        dp[i] = d[i].p;
+    }
+    for (size_t i = 0; i < N; ++i)
+        if (b[i].host && b[i].in) LR_HIP(hipMemcpy(dp[i], b[i].host, b[i].bytes, hipMemcpyHostToDevice));
+    if (const int rc = launch(dp)) return rc;
+    LR_HIP(hipDeviceSynchronize());
+    for (size_t i = 0; i < N; ++i)
+        if (b[i].host && b[i].out) LR_HIP(hipMemcpy(b[i].host, dp[i], b[i].bytes, hipMemcpyDeviceToHost));
+    return LR_OK;
+}
 
-int run_common(lr_model* m, const RunSpec& rs, const lr_run_opts* o, void* state, double* lp_state, void* out,
-               uint32_t* accepts) {
+// The arrays of a run.  tally: accept counts (uint32 per chain) or NUTS counters, tally_item bytes per chain; launches add to it, so it
+// is copied in as well as out.  lp_state: RWMH / MALA only.  depth_out: NUTS only.
+struct RunArrays {
+    void* state;
+    double* lp_state;
+    void* out;
+    void* tally;
+    size_t tally_item;
+    int8_t* depth_out;
+};
+
+// The front every lr_run_* shares, after the checks of its own parameters: check the options and arrays, plan, then either enqueue on
+// the caller's stream over the caller's device buffers or stage host arrays (the statistics buffer is staged like the others, through a
+// device-side view of the options).  launch(plan, stream, opts, arrays) is the family's launch.
+template <typename Launch>
+int run_request(lr_model* m, int kind, int max_depth, const lr_run_opts* o, const RunArrays& a, Launch&& launch) {
     int rc = check_opts(m, o, true);
     if (rc) return rc;
-    if (!state) return fail(LR_ERR_INVALID, "state is NULL");
-    const bool threaded = rs.kind == lr::KIND_RWMH || rs.kind == lr::KIND_MALA;
-    if (threaded && !lp_state) return fail(LR_ERR_INVALID, "lp_state is required for RWMH/MALA");
+    if (!a.state) return fail(LR_ERR_INVALID, "state is NULL");
+    if ((kind == LR_KIND_RWMH || kind == LR_KIND_MALA) && !a.lp_state) return fail(LR_ERR_INVALID, "lp_state is required for RWMH/MALA");
     LR_HIP(hipSetDevice(m->device));
     Plan pl;
-    rc = make_plan(m, plan_count(o), o->group, o->mode, &pl, false, rs.kind == lr::KIND_HMC && o->precision != LR_PREC_FULL, rs.kind,
-                   o->precision == LR_PREC_AUTO);
+    rc = plan_run(m, kind, o, max_depth, &pl);
     if (rc) return rc;
     if (o->iters == 0) return LR_OK;
-    if (o->on_device) return do_chain(m, pl, (hipStream_t)o->stream, rs, o, state, threaded ? lp_state : nullptr, out, accepts);
+    if (o->on_device) return launch(pl, (hipStream_t)o->stream, o, a);
+    const size_t C = (size_t)o->n_chains, sbytes = C * m->p * m->esize();
+    const HostBuf b[] = {{a.state, sbytes, true, true}, {a.lp_state, C * sizeof(double), true, true}, {a.out, (size_t)o->iters * sbytes, false, true},
+                         {a.tally, C * a.tally_item, true, true}, {a.depth_out, (size_t)o->iters * C, false, true},
+                         {o->stats, (size_t)o->stats_slots * C * 2 * m->p * sizeof(double), true, true}};
+    return staged(b, [&](void* const* d) {
+        lr_run_opts od = *o;
+        od.stats = static_cast<double*>(d[5]);
+        return launch(pl, nullptr, &od, RunArrays{d[0], static_cast<double*>(d[1]), d[2], d[3], a.tally_item, static_cast<int8_t*>(d[4])});
+    });
+}
 
-    const size_t es = m->esize();
-    const size_t sbytes = (size_t)o->n_chains * m->p * es;
-    const size_t obytes = out ? (size_t)o->iters * o->n_chains * m->p * es : 0;
-    DevBuf ds, dl, dout, dacc, dstats;
-    if (ds.alloc(sbytes) || dl.alloc(o->n_chains * sizeof(double)) || dout.alloc(obytes) ||
-        dacc.alloc(o->n_chains * sizeof(uint32_t)))
-        return fail(LR_ERR_NOMEM, "device allocation failed (%zu bytes of samples)", obytes);
-    lr_run_opts od = *o;  // device-side view of the options: the statistics buffer is staged like the other arrays
-    const size_t stbytes = o->stats ? (size_t)o->stats_slots * o->n_chains * 2 * m->p * sizeof(double) : 0;
-    if (o->stats) {
-        if (dstats.alloc(stbytes)) return fail(LR_ERR_NOMEM, "device allocation failed (%zu bytes of statistics)", stbytes);
-        LR_HIP(hipMemcpy(dstats.p, o->stats, stbytes, hipMemcpyHostToDevice));
-        od.stats = static_cast<double*>(dstats.p);
-    }
-    LR_HIP(hipMemcpy(ds.p, state, sbytes, hipMemcpyHostToDevice));
-    if (threaded) LR_HIP(hipMemcpy(dl.p, lp_state, o->n_chains * sizeof(double), hipMemcpyHostToDevice));
-    if (accepts) LR_HIP(hipMemcpy(dacc.p, accepts, o->n_chains * sizeof(uint32_t), hipMemcpyHostToDevice));
-    rc = do_chain(m, pl, nullptr, rs, &od, ds.p, threaded ? (double*)dl.p : nullptr, out ? dout.p : nullptr,
-                  accepts ? (uint32_t*)dacc.p : nullptr);
-    if (rc) return rc;
-    LR_HIP(hipDeviceSynchronize());
-    if (o->stats) LR_HIP(hipMemcpy(o->stats, dstats.p, stbytes, hipMemcpyDeviceToHost));
-    LR_HIP(hipMemcpy(state, ds.p, sbytes, hipMemcpyDeviceToHost));
-    if (threaded) LR_HIP(hipMemcpy(lp_state, dl.p, o->n_chains * sizeof(double), hipMemcpyDeviceToHost));
-    if (out) LR_HIP(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
-    if (accepts) LR_HIP(hipMemcpy(accepts, dacc.p, o->n_chains * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return LR_OK;
+int run_common(lr_model* m, const RunSpec& rs, const lr_run_opts* o, void* state, double* lp_state, void* out, uint32_t* accepts) {
+    return run_request(m, rs.kind, 0, o, RunArrays{state, lp_state, out, accepts, sizeof(uint32_t), nullptr},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
+                           return do_chain(m, pl, st, rs, oo, d.state, d.lp_state, d.out, static_cast<uint32_t*>(d.tally));
+                       });
 }
 
 static_assert(sizeof(lr::NutsCounters) == sizeof(lr_nuts_counters), "lr_nuts_counters layout");
@@ -160,7 +192,8 @@ int do_nuts_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o,
 }
 int do_nuts(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
             void* out, lr_nuts_counters* counters, int8_t* depth_out) {
-    LR_DISPATCH_TP(m, do_nuts_t, m, pl, st, o, eps, max_depth, dmm, state, out, counters, depth_out);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_nuts_t, m, pl, st, o, eps, max_depth, dmm, state, out, counters, depth_out)
+    return bad_width(m);
 }
 
 int positive_vec(const char* name, const double* v, int p) {
@@ -169,6 +202,35 @@ int positive_vec(const char* name, const double* v, int p) {
         if (!(v[j] > 0) || !std::isfinite(v[j])) return fail(LR_ERR_INVALID, "%s[%d] must be finite and > 0", name, j);
     return LR_OK;
 }
+
+// signed rows  xs_i = s_i x_i  of a design X [n][p], zero-padded to P columns, in the compute dtype;  s_i = 2 y_i - 1, or 1 without labels
+// (`sign`, where given, receives them).  `name` is the caller's word for X in the message.
+int signed_rows(const char* name, const double* X, const double* y, int64_t n, int p, int P, int dtype, std::vector<unsigned char>* host, signed char* sign) {
+    host->resize((size_t)n * P * (dtype == LR_F32 ? 4 : 8));
+    for (int64_t i = 0; i < n; ++i) {
+        const double s = y ? 2.0 * y[i] - 1.0 : 1.0;
+        if (sign) sign[i] = (signed char)s;
+        for (int j = 0; j < P; ++j) {
+            const double v = j < p ? s * X[i * p + j] : 0.0;
+            if (!std::isfinite(v)) return fail(LR_ERR_INVALID, "%s[%lld,%d] is not finite", name, (long long)i, j);
+            if (dtype == LR_F32) reinterpret_cast<float*>(host->data())[i * P + j] = (float)v;
+            else reinterpret_cast<double*>(host->data())[i * P + j] = v;
+        }
+    }
+    return LR_OK;
+}
+
+// One device array of a handle under construction: allocate, copy.  *dptr is the handle's field, so the handle's destroy call frees it
+// whichever step fails.  copy_fail: the status of a failing copy (the operand images report LR_ERR_NOMEM for either step).
+int upload(const char* who, const char* what, const void* host, size_t bytes, void** dptr, int copy_fail) {
+    if (hipMalloc(dptr, bytes) != hipSuccess) return fail(LR_ERR_NOMEM, "%s: allocating the %s (%zu bytes) failed", who, what, bytes);
+    const hipError_t e = hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(copy_fail, "%s: copying the %s (%zu bytes) failed: %s", who, what, bytes, hipGetErrorString(e));
+    return LR_OK;
+}
+
+template <int P> size_t wide_block_elems() { return lr::WideBf16Geom<P>::BUF; }
+template <int P> size_t wide_block1_elems() { return lr::WideBf16Geom<P>::BUF1; }
 
 }  // namespace
 
@@ -223,23 +285,21 @@ int lr_model_create(const double* X, const double* y, int64_t n, int32_t p, cons
     if (device < 0 || device >= ndev) return fail(LR_ERR_HIP, "device %d not available (%d visible)", device, ndev);
     LR_HIP(hipSetDevice(device));
 
-    lr_model* m = new lr_model();
-    {
-        char bad[64];
-        if (!parse_debug_opts(std::getenv("LOGREG_DEBUG_OPTS"), &m->dbg, bad, sizeof bad)) {
-            delete m;
-            return fail(LR_ERR_INVALID, "LOGREG_DEBUG_OPTS: unknown or out-of-range item '%s' (keys: residency_cap=0|1, tall_mx16=0|1, "
-                                        "wide_traj=0|1|2, wide_waves=4|8, wide_f16=0|1|2)", bad);
-        }
-    }
+    std::unique_ptr<lr_model, decltype(&lr_model_destroy)> guard(new lr_model(), lr_model_destroy);  // every failure below destroys what exists
+    lr_model* m = guard.get();
     m->device = device;
+    char bad[64];
+    if (!parse_debug_opts(std::getenv("LOGREG_DEBUG_OPTS"), &m->dbg, bad, sizeof bad))
+        return fail(LR_ERR_INVALID, "LOGREG_DEBUG_OPTS: unknown or out-of-range item '%s' (keys: residency_cap=0|1, tall_mx16=0|1, "
+                                    "wide_traj=0|1|2, wide_waves=4|8, wide_f16=0|1|2)", bad);
     m->dtype = dtype;
     m->n = n;
     m->p = p;
     m->P = padded_width(p);
-    const ModelImages images = model_images(n, m->P, dtype);
-    m->table = find_table(dtype, m->P);
-    if (!m->table) { delete m; return fail(LR_ERR_UNSUPPORTED, "no kernels for dtype=%d padded p=%d", dtype, m->P); }
+    const int P = m->P;
+    const ModelImages images = model_images(n, P, dtype);
+    m->table = find_table(dtype, P);
+    if (!m->table) return fail(LR_ERR_UNSUPPORTED, "no kernels for dtype=%d padded p=%d", dtype, P);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) m->cus = prop.multiProcessorCount;
     m->lprior_const = 0;
@@ -248,132 +308,71 @@ int lr_model_create(const double* X, const double* y, int64_t n, int32_t p, cons
         m->inv_var[j] = 1.0 / (prior_sd[j] * prior_sd[j]);
         m->lprior_const += -std::log(prior_sd[j]) - 0.91893853320467274178;
     }
-    // signed rows  xs_i = (2 y_i - 1) x_i, zero-padded to P columns, in the compute dtype
-    const size_t elems = (size_t)n * m->P;
-    std::vector<unsigned char> host(elems * m->esize());
+    const auto image = [](const char* what, const void* host, size_t bytes, void** dptr) { return upload("lr_model_create", what, host, bytes, dptr, LR_ERR_NOMEM); };
+    std::vector<unsigned char> host;
     m->ysign.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const double s = 2.0 * y[i] - 1.0;
-        m->ysign[(size_t)i] = (signed char)s;
-        for (int j = 0; j < m->P; ++j) {
-            const double v = j < p ? s * X[i * p + j] : 0.0;
-            if (!std::isfinite(v)) { delete m; return fail(LR_ERR_INVALID, "X[%lld,%d] is not finite", (long long)i, j); }
-            if (dtype == LR_F32) reinterpret_cast<float*>(host.data())[i * m->P + j] = (float)v;
-            else reinterpret_cast<double*>(host.data())[i * m->P + j] = v;
-        }
+    if ((rc = signed_rows("X", X, y, n, p, P, dtype, &host, m->ysign.data()))) return rc;
+    if ((rc = upload("lr_model_create", "rows", host.data(), host.size(), &m->d_rows, LR_ERR_HIP))) return rc;
+    // the rows as float32, for the operand images (float64 models: rounded once, where an image is built from them)
+    std::vector<float> rounded;
+    if (dtype != LR_F32 && (images.tall_mx || images.wide1)) {
+        const double* h64 = reinterpret_cast<const double*>(host.data());
+        rounded.assign(h64, h64 + (size_t)n * P);
     }
-    if (hipMalloc(&m->d_rows, host.size()) != hipSuccess) { delete m; return fail(LR_ERR_NOMEM, "hipMalloc rows failed"); }
-    if (hipMemcpy(m->d_rows, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(m->d_rows);
-        delete m;
-        return fail(LR_ERR_HIP, "hipMemcpy rows failed");
-    }
-    if (m->P <= 32 && dtype == LR_F32) {
+    const float* hrows = dtype == LR_F32 ? reinterpret_cast<const float*>(host.data()) : rounded.data();
+    if (P <= 32 && dtype == LR_F32) {
         // the rows once more as twisted row pairs, for the kernels that take them through the scalar unit:
         // pair k, coordinates (j, j+1), j even:  [k][j] = (A_j, B_{j+1}),  [k][j+1] = (A_{j+1}, B_j)  with
         // A = row 2k, B = row 2k+1 (a zero row closes an odd n)
-        const float* hrows = reinterpret_cast<const float*>(host.data());
         const int64_t npair = (n + 1) / 2;
-        const int PP = m->P;
-        std::vector<float> tw((size_t)npair * PP * 2, 0.0f);
-        auto at = [&](int64_t r, int j) { return r < n ? hrows[r * PP + j] : 0.0f; };
+        std::vector<float> tw((size_t)npair * P * 2, 0.0f);
+        auto at = [&](int64_t r, int j) { return r < n ? hrows[r * P + j] : 0.0f; };
         for (int64_t k = 0; k < npair; ++k)
-            for (int j = 0; j < PP; j += 2) {
-                float* q = tw.data() + ((size_t)k * PP + j) * 2;
+            for (int j = 0; j < P; j += 2) {
+                float* q = tw.data() + ((size_t)k * P + j) * 2;
                 q[0] = at(2 * k, j);
                 q[1] = at(2 * k + 1, j + 1);
                 q[2] = at(2 * k, j + 1);
                 q[3] = at(2 * k + 1, j);
             }
-        if (hipMalloc(&m->d_rows_tw, tw.size() * 4) != hipSuccess ||
-            hipMemcpy(m->d_rows_tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            lr_model_destroy(m);
-            return fail(LR_ERR_NOMEM, "allocating the row-pair image (%zu bytes) failed", tw.size() * 4);
-        }
+        if ((rc = image("row-pair image", tw.data(), tw.size() * 4, &m->d_rows_tw))) return rc;
     }
     // narrow models the planner would ever send to the stepwise engine by itself (rows beyond 64 KB): two-piece bf16 tile images
     // for the interior HMC steps on the matrix pipe.  Smaller models run the engine only when forced (mode = STEPWISE), then in
     // fp32 throughout, and carry no image.
     if (images.tall_mx) {
-        std::vector<float> rounded;
-        if (dtype != LR_F32) {
-            rounded.resize(elems);
-            for (size_t i = 0; i < elems; ++i) rounded[i] = (float)reinterpret_cast<const double*>(host.data())[i];
-        }
-        const float* hrows = dtype == LR_F32 ? reinterpret_cast<const float*>(host.data()) : rounded.data();
         const int64_t ntile = (n + 31) / 32 * 2;
-        std::vector<uint16_t> img((size_t)ntile * (m->P / 8) * lr::kMxSetElems);
-        if (m->P == 8) lr::tall_mx_prepare<8>(hrows, n, img.data());
-        else if (m->P == 16) lr::tall_mx_prepare<16>(hrows, n, img.data());
-        else lr::tall_mx_prepare<32>(hrows, n, img.data());
-        if (hipMalloc(&m->d_xmx, img.size() * 2) != hipSuccess ||
-            hipMemcpy(m->d_xmx, img.data(), img.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-            lr_model_destroy(m);
-            return fail(LR_ERR_NOMEM, "allocating the bf16 tile images (%zu bytes) failed", img.size() * 2);
-        }
+        std::vector<uint16_t> img((size_t)ntile * (P / 8) * lr::kMxSetElems);
+        LR_BY_WIDTH_MX(P, lr::tall_mx_prepare, hrows, n, img.data());
+        if ((rc = image("bf16 tile images", img.data(), img.size() * 2, &m->d_xmx))) return rc;
     }
     if (images.mf_end) {  // (up to 8192 rows: profiles/r2_midn_lds_mfma.txt)
         // the matrix-core chain kernel would keep its bf16 operands in LDS: fp32 operand images for its end points
-        const float* hrows = reinterpret_cast<const float*>(host.data());
-        const size_t fl = (size_t)((n + 15) / 16) * 64 *
-                          (m->P == 8 ? lr::mf_image_floats<8>() : (m->P == 16 ? lr::mf_image_floats<16>() : lr::mf_image_floats<32>()));
-        std::vector<float> img(fl);
-        if (m->P == 8) lr::mf_image_prepare<8>(hrows, n, img.data());
-        else if (m->P == 16) lr::mf_image_prepare<16>(hrows, n, img.data());
-        else lr::mf_image_prepare<32>(hrows, n, img.data());
-        if (hipMalloc(&m->d_xmf, fl * 4) != hipSuccess || hipMemcpy(m->d_xmf, img.data(), fl * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            lr_model_destroy(m);
-            return fail(LR_ERR_NOMEM, "allocating the fp32 operand images (%zu bytes) failed", fl * 4);
-        }
+        std::vector<float> img((size_t)((n + 15) / 16) * 64 * LR_BY_WIDTH_MX(P, lr::mf_image_floats));
+        LR_BY_WIDTH_MX(P, lr::mf_image_prepare, hrows, n, img.data());
+        if ((rc = image("fp32 operand images", img.data(), img.size() * 4, &m->d_xmf))) return rc;
         if (model_wants_xms(m) && m->table->mfma_image_bytes && m->table->launch_mfma_image) {
             const size_t ib = m->table->mfma_image_bytes(n);  // beyond LDS: the interior operands, built on the device once
             if (hipMalloc(&m->d_xms, ib) != hipSuccess || m->table->launch_mfma_image(nullptr, m->d_rows, n, m->d_xms) != 0 ||
-                hipDeviceSynchronize() != hipSuccess) {
-                lr_model_destroy(m);
+                hipDeviceSynchronize() != hipSuccess)
                 return fail(LR_ERR_NOMEM, "building the bf16 operand images (%zu bytes) failed", ib);
-            }
         }
     }
+    const int64_t nblk = (n + 31) / 32;
     if (images.wide) {  // wide float32 models: bf16-piece block images for the exact-split matrix-core kernels
-        const float* hrows = reinterpret_cast<const float*>(host.data());
-        const int64_t nblk = (n + 31) / 32;
-        const size_t elems_blk = m->P == 64 ? (size_t)lr::WideBf16Geom<64>::BUF : (size_t)lr::WideBf16Geom<128>::BUF;
-        std::vector<uint16_t> img((size_t)nblk * elems_blk);
-        if (m->P == 64) lr::wide_bf16_prepare<64>(hrows, n, img.data());
-        else lr::wide_bf16_prepare<128>(hrows, n, img.data());
-        if (hipMalloc(&m->d_xblk, img.size() * 2) != hipSuccess ||
-            hipMemcpy(m->d_xblk, img.data(), img.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-            lr_model_destroy(m);
-            return fail(LR_ERR_NOMEM, "allocating the bf16 block images (%zu bytes) failed", img.size() * 2);
-        }
+        std::vector<uint16_t> img((size_t)nblk * LR_BY_WIDTH_WIDE(P, wide_block_elems));
+        LR_BY_WIDTH_WIDE(P, lr::wide_bf16_prepare, hrows, n, img.data());
+        if ((rc = image("bf16 block images", img.data(), img.size() * 2, &m->d_xblk))) return rc;
     }
     if (images.wide1) {  // ... and the one-piece image (float64 models: from the rows rounded to float32)
-        std::vector<float> rounded;
-        if (dtype != LR_F32) {
-            rounded.resize(elems);
-            for (size_t i = 0; i < elems; ++i) rounded[i] = (float)reinterpret_cast<const double*>(host.data())[i];
-        }
-        const float* hrows = dtype == LR_F32 ? reinterpret_cast<const float*>(host.data()) : rounded.data();
-        const int64_t nblk = (n + 31) / 32;
-        const size_t elems_blk1 = m->P == 64 ? (size_t)lr::WideBf16Geom<64>::BUF1 : (size_t)lr::WideBf16Geom<128>::BUF1;
-        std::vector<uint16_t> img1((size_t)nblk * elems_blk1);
-        if (m->P == 64) lr::wide_bf16_prepare_rne<64>(hrows, n, img1.data());
-        else lr::wide_bf16_prepare_rne<128>(hrows, n, img1.data());
-        if (hipMalloc(&m->d_xblk1, img1.size() * 2) != hipSuccess ||
-            hipMemcpy(m->d_xblk1, img1.data(), img1.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-            lr_model_destroy(m);
-            return fail(LR_ERR_NOMEM, "allocating the single-piece bf16 block images (%zu bytes) failed", img1.size() * 2);
-        }
-        {  // the interior kernels' half-precision image, where the rows fit its range (lr_wide_bf16.h)
-            const bool fits = m->P == 64 ? lr::wide_f16_prepare_rne<64>(hrows, n, img1.data()) : lr::wide_f16_prepare_rne<128>(hrows, n, img1.data());
-            if (fits && (hipMalloc(&m->d_xblk1h, img1.size() * 2) != hipSuccess ||
-                         hipMemcpy(m->d_xblk1h, img1.data(), img1.size() * 2, hipMemcpyHostToDevice) != hipSuccess)) {
-                lr_model_destroy(m);
-                return fail(LR_ERR_NOMEM, "allocating the single-piece f16 block images (%zu bytes) failed", img1.size() * 2);
-            }
-        }
+        std::vector<uint16_t> img1((size_t)nblk * LR_BY_WIDTH_WIDE(P, wide_block1_elems));
+        LR_BY_WIDTH_WIDE(P, lr::wide_bf16_prepare_rne, hrows, n, img1.data());
+        if ((rc = image("single-piece bf16 block images", img1.data(), img1.size() * 2, &m->d_xblk1))) return rc;
+        // the interior kernels' half-precision image, where the rows fit its range (lr_wide_bf16.h)
+        if (LR_BY_WIDTH_WIDE(P, lr::wide_f16_prepare_rne, hrows, n, img1.data()))
+            if ((rc = image("single-piece f16 block images", img1.data(), img1.size() * 2, &m->d_xblk1h))) return rc;
     }
-    *out = m;
+    *out = guard.release();
     return LR_OK;
 }
 
@@ -429,7 +428,7 @@ int lr_plan(const lr_model* m, int64_t n_chains, int32_t group, int32_t mode, in
     if (n_chains <= 0) return fail(LR_ERR_INVALID, "n_chains must be positive (got %lld)", (long long)n_chains);
     if (const int rcg = check_group_for(m, group, mode)) return rcg;
     Plan pl;
-    const int rc = make_plan(m, n_chains, group, mode, &pl);
+    const int rc = make_plan(plan_request(m, n_chains, group, mode), &pl);
     if (rc) return rc;
     if (mode_out) *mode_out = pl.mode;
     if (group_out) *group_out = pl.G;
@@ -443,26 +442,19 @@ int lr_plan_run_info(const lr_model* m, int32_t kind, const lr_run_opts* o, lr_p
     if (rc) return rc;
     if (kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
     Plan pl;
-    rc = kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, LR_NUTS_MAX_DEPTH, &pl)
-                              : make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
-                                          o->precision == LR_PREC_AUTO);
+    rc = plan_run(m, kind, o, LR_NUTS_MAX_DEPTH, &pl);
     if (rc) return rc;
     *out = lr_plan_info{pl.mode, pl.G, pl.R, pl.G2, pl.R2, pl.split, pl.mode2, 0};
     return LR_OK;
 }
 
 int lr_plan_run(const lr_model* m, int32_t kind, const lr_run_opts* o, int32_t* mode_out, int32_t* group_out, int32_t* rows_out) {
-    int rc = check_opts(m, o, false);
+    lr_plan_info pi;
+    const int rc = lr_plan_run_info(m, kind, o, &pi);
     if (rc) return rc;
-    if (kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
-    Plan pl;
-    rc = kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, LR_NUTS_MAX_DEPTH, &pl)
-                              : make_plan(m, plan_count(o), o->group, o->mode, &pl, false, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, kind,
-                                          o->precision == LR_PREC_AUTO);
-    if (rc) return rc;
-    if (mode_out) *mode_out = pl.mode;
-    if (group_out) *group_out = pl.G;
-    if (rows_out) *rows_out = pl.R;
+    if (mode_out) *mode_out = pi.mode;
+    if (group_out) *group_out = pi.group;
+    if (rows_out) *rows_out = pi.rows;
     return LR_OK;
 }
 
@@ -472,24 +464,14 @@ int lr_eval(lr_model* m, const void* beta, void* ll, void* lprior, void* lpost, 
     if (!beta) return fail(LR_ERR_INVALID, "beta is NULL");
     LR_HIP(hipSetDevice(m->device));
     Plan pl;
-    rc = make_plan(m, o->n_chains, o->group, o->mode, &pl, true);
+    rc = make_plan(plan_request_eval(m, o), &pl);
     if (rc) return rc;
     const int64_t C = o->n_chains;
     if (o->on_device) return do_eval(m, pl, (hipStream_t)o->stream, C, beta, ll, lprior, lpost, grad);
-    const size_t es = m->esize();
-    DevBuf db, dll, dlpr, dlpo, dg;
-    if (db.alloc(C * m->p * es) || dll.alloc(C * es) || dlpr.alloc(C * es) || dlpo.alloc(C * es) || dg.alloc(C * m->p * es))
-        return fail(LR_ERR_NOMEM, "device allocation failed");
-    LR_HIP(hipMemcpy(db.p, beta, C * m->p * es, hipMemcpyHostToDevice));
-    rc = do_eval(m, pl, nullptr, C, db.p, ll ? dll.p : nullptr, lprior ? dlpr.p : nullptr, lpost ? dlpo.p : nullptr,
-                 grad ? dg.p : nullptr);
-    if (rc) return rc;
-    LR_HIP(hipDeviceSynchronize());
-    if (ll) LR_HIP(hipMemcpy(ll, dll.p, C * es, hipMemcpyDeviceToHost));
-    if (lprior) LR_HIP(hipMemcpy(lprior, dlpr.p, C * es, hipMemcpyDeviceToHost));
-    if (lpost) LR_HIP(hipMemcpy(lpost, dlpo.p, C * es, hipMemcpyDeviceToHost));
-    if (grad) LR_HIP(hipMemcpy(grad, dg.p, C * m->p * es, hipMemcpyDeviceToHost));
-    return LR_OK;
+    const size_t one = (size_t)C * m->esize(), vec = one * m->p;
+    const HostBuf b[] = {{const_cast<void*>(beta), vec, true, false}, {ll, one, false, true}, {lprior, one, false, true}, {lpost, one, false, true},
+                         {grad, vec, false, true}};
+    return staged(b, [&](void* const* d) { return do_eval(m, pl, nullptr, C, d[0], d[1], d[2], d[3], d[4]); });
 }
 
 int lr_run_rwmh(lr_model* m, void* state, double* lp_state, const double* prop_sd, const lr_run_opts* o, void* out,
@@ -561,44 +543,12 @@ int lr_run_nuts(lr_model* m, void* state, double eps, int32_t max_depth, const d
     if (!m) return fail(LR_ERR_INVALID, "model is NULL");
     if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
     if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
-    int rc = positive_vec("dmm", dmm, m->p);
+    const int rc = positive_vec("dmm", dmm, m->p);
     if (rc) return rc;
-    rc = check_opts(m, o, true);
-    if (rc) return rc;
-    if (!state) return fail(LR_ERR_INVALID, "state is NULL");
-    LR_HIP(hipSetDevice(m->device));
-    Plan pl;
-    rc = plan_nuts(m, o->group, o->mode, max_depth, &pl);
-    if (rc) return rc;
-    if (o->iters == 0) return LR_OK;
-    if (o->on_device) return do_nuts(m, pl, (hipStream_t)o->stream, o, eps, max_depth, dmm, state, out, counters, depth_out);
-
-    const int64_t C = o->n_chains;
-    const size_t sbytes = (size_t)C * m->p * m->esize();
-    const size_t obytes = out ? (size_t)o->iters * C * m->p * m->esize() : 0;
-    const size_t cbytes = counters ? (size_t)C * sizeof(lr_nuts_counters) : 0;
-    const size_t dbytes = depth_out ? (size_t)o->iters * C : 0;
-    const size_t stbytes = o->stats ? (size_t)o->stats_slots * C * 2 * m->p * sizeof(double) : 0;
-    DevBuf ds, dout, dcnt, ddep, dstats;
-    if (ds.alloc(sbytes) || dout.alloc(obytes) || dcnt.alloc(cbytes) || ddep.alloc(dbytes) || dstats.alloc(stbytes))
-        return fail(LR_ERR_NOMEM, "device allocation failed (%zu bytes of samples)", obytes);
-    lr_run_opts od = *o;
-    if (o->stats) {
-        LR_HIP(hipMemcpy(dstats.p, o->stats, stbytes, hipMemcpyHostToDevice));
-        od.stats = static_cast<double*>(dstats.p);
-    }
-    LR_HIP(hipMemcpy(ds.p, state, sbytes, hipMemcpyHostToDevice));
-    if (counters) LR_HIP(hipMemcpy(dcnt.p, counters, cbytes, hipMemcpyHostToDevice));
-    rc = do_nuts(m, pl, nullptr, &od, eps, max_depth, dmm, ds.p, out ? dout.p : nullptr, counters ? (lr_nuts_counters*)dcnt.p : nullptr,
-                 depth_out ? (int8_t*)ddep.p : nullptr);
-    if (rc) return rc;
-    LR_HIP(hipDeviceSynchronize());
-    if (o->stats) LR_HIP(hipMemcpy(o->stats, dstats.p, stbytes, hipMemcpyDeviceToHost));
-    LR_HIP(hipMemcpy(state, ds.p, sbytes, hipMemcpyDeviceToHost));
-    if (out) LR_HIP(hipMemcpy(out, dout.p, obytes, hipMemcpyDeviceToHost));
-    if (counters) LR_HIP(hipMemcpy(counters, dcnt.p, cbytes, hipMemcpyDeviceToHost));
-    if (depth_out) LR_HIP(hipMemcpy(depth_out, ddep.p, dbytes, hipMemcpyDeviceToHost));
-    return LR_OK;
+    return run_request(m, LR_KIND_NUTS, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
+                           return do_nuts(m, pl, st, oo, eps, max_depth, dmm, d.state, d.out, static_cast<lr_nuts_counters*>(d.tally), d.depth_out);
+                       });
 }
 
 int lr_hessian(lr_model* m, const double* beta, double* lpost, double* grad, double* hess, void* stream) {
@@ -733,7 +683,7 @@ int pred_launch(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) 
     return LR_OK;
 }
 int pred_launch_any(lr_predict* pp, const void* d_draws, int64_t S, hipStream_t st) {
-    LR_RETURN_BY_DTYPE_WIDTH(pp->m->dtype, pp->m->P, pred_launch, pp, d_draws, S, st)
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, pp->m->dtype, pp->m->P, pred_launch, pp, d_draws, S, st)
     return fail(LR_ERR_UNSUPPORTED, "lr_predict: unsupported padded width %d", pp->m->P);
 }
 }  // namespace
@@ -749,7 +699,6 @@ int lr_predict_create(lr_model* m, const double* X_new, const double* y_new, int
         for (int64_t i = 0; i < r; ++i)
             if (y_new[i] != 0.0 && y_new[i] != 1.0) return fail(LR_ERR_INVALID, "lr_predict_create: y_new[%lld]=%g is not 0/1", (long long)i, y_new[i]);
     LR_HIP(hipSetDevice(m->device));
-    hipError_t e;
     lr_predict* pp = new lr_predict();
     pp->m = m;
     pp->device = m->device;
@@ -757,40 +706,24 @@ int lr_predict_create(lr_model* m, const double* X_new, const double* y_new, int
     pp->labels = !X_new || y_new;
     std::vector<signed char> sg;
     if (X_new) {
-        const int p = m->p, P = m->P;
-        std::vector<unsigned char> host((size_t)r * P * m->esize());
+        std::vector<unsigned char> host;
         if (y_new) sg.resize((size_t)r);
-        for (int64_t i = 0; i < r; ++i) {
-            const double s = y_new ? 2.0 * y_new[i] - 1.0 : 1.0;
-            if (y_new) sg[(size_t)i] = (signed char)s;
-            for (int j = 0; j < P; ++j) {
-                const double v = j < p ? s * X_new[i * p + j] : 0.0;
-                if (!std::isfinite(v)) { delete pp; return fail(LR_ERR_INVALID, "lr_predict_create: X_new[%lld,%d] is not finite", (long long)i, j); }
-                if (m->dtype == LR_F32) reinterpret_cast<float*>(host.data())[i * P + j] = (float)v;
-                else reinterpret_cast<double*>(host.data())[i * P + j] = v;
-            }
-        }
         pp->own_rows = true;
-        if (hipMalloc(&pp->d_rows, host.size()) != hipSuccess) {
+        int rc = signed_rows("lr_predict_create: X_new", X_new, y_new, r, m->p, m->P, m->dtype, &host, y_new ? sg.data() : nullptr);
+        if (!rc) rc = upload("lr_predict_create", "rows", host.data(), host.size(), &pp->d_rows, LR_ERR_HIP);
+        if (rc) {
             lr_predict_destroy(pp);
-            return fail(LR_ERR_NOMEM, "lr_predict_create: allocating %zu bytes of rows failed", host.size());
-        }
-        if ((e = hipMemcpy(pp->d_rows, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-            lr_predict_destroy(pp);
-            return fail(LR_ERR_HIP, "lr_predict_create: copying the rows failed: %s", hipGetErrorString(e));
+            return rc;
         }
     } else {
         pp->d_rows = m->d_rows;
     }
     const std::vector<signed char>& signs = X_new ? sg : m->ysign;
-    if (pp->labels && hipMalloc((void**)&pp->d_sign, (size_t)r) != hipSuccess) {
-        lr_predict_destroy(pp);
-        return fail(LR_ERR_NOMEM, "lr_predict_create: allocating the labels failed");
-    }
-    if (pp->labels && (e = hipMemcpy(pp->d_sign, signs.data(), (size_t)r, hipMemcpyHostToDevice)) != hipSuccess) {
-        lr_predict_destroy(pp);
-        return fail(LR_ERR_HIP, "lr_predict_create: copying the labels failed: %s", hipGetErrorString(e));
-    }
+    if (pp->labels)
+        if (const int rc = upload("lr_predict_create", "labels", signs.data(), (size_t)r, (void**)&pp->d_sign, LR_ERR_HIP)) {
+            lr_predict_destroy(pp);
+            return rc;
+        }
     if (hipMalloc((void**)&pp->d_acc, (size_t)LR_PRED_ROWS * r * sizeof(double)) != hipSuccess) {
         lr_predict_destroy(pp);
         return fail(LR_ERR_NOMEM, "lr_predict_create: allocating the table failed");
@@ -1156,7 +1089,7 @@ int cov_launch(lr_cov* h, const void* d_block, int64_t k, hipStream_t st) {
     return LR_OK;
 }
 int cov_launch_any(lr_cov* h, const void* d_block, int64_t k, hipStream_t st) {
-    LR_RETURN_BY_DTYPE_WIDTH(h->dtype, h->P, cov_launch, h, d_block, k, st)
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, h->dtype, h->P, cov_launch, h, d_block, k, st)
     return fail(LR_ERR_UNSUPPORTED, "lr_cov: unsupported padded width %d", h->P);
 }
 }  // namespace
@@ -1313,7 +1246,7 @@ int loo_fill(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
     return LR_OK;
 }
 int loo_fill_any(lr_loo* a, const void* d_draws, int64_t S, hipStream_t st) {
-    LR_RETURN_BY_DTYPE_WIDTH(a->m->dtype, a->m->P, loo_fill, a, d_draws, S, st)
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, a->m->dtype, a->m->P, loo_fill, a, d_draws, S, st)
     return fail(LR_ERR_UNSUPPORTED, "lr_loo: unsupported padded width %d", a->m->P);
 }
 

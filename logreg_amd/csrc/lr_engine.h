@@ -18,9 +18,6 @@ template <typename T, int P> lr::ModelArgs<T, P> model_args(const lr_model* m) {
     return a;
 }
 
-// the chain count every chain-count-dependent choice is made for (lr_run_opts.plan_chains: a shard plans as the whole run)
-int64_t plan_count(const lr_run_opts* o) { return o->plan_chains > 0 ? (int64_t)o->plan_chains : o->n_chains; }
-
 struct RunSpec {
     int kind;
     double step;
@@ -384,25 +381,7 @@ int do_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs
     return LR_OK;
 }
 
-#define LR_DISPATCH_TP(m, FN, ...)                                                       \
-    do {                                                                                 \
-        if ((m)->dtype == LR_F32) {                                                      \
-            switch ((m)->P) {                                                            \
-            case 4: return FN<float, 4>(__VA_ARGS__);                                    \
-            case 8: return FN<float, 8>(__VA_ARGS__);                                    \
-            case 16: return FN<float, 16>(__VA_ARGS__);                                  \
-            case 32: return FN<float, 32>(__VA_ARGS__);                                  \
-            }                                                                            \
-        } else {                                                                         \
-            switch ((m)->P) {                                                            \
-            case 4: return FN<double, 4>(__VA_ARGS__);                                   \
-            case 8: return FN<double, 8>(__VA_ARGS__);                                   \
-            case 16: return FN<double, 16>(__VA_ARGS__);                                 \
-            case 32: return FN<double, 32>(__VA_ARGS__);                                 \
-            }                                                                            \
-        }                                                                                \
-        return fail(LR_ERR_UNSUPPORTED, "unsupported padded width %d", (m)->P);          \
-    } while (0)
+int bad_width(const lr_model* m) { return fail(LR_ERR_UNSUPPORTED, "unsupported padded width %d", m->P); }
 
 int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
                      void* lpost, void* grad);
@@ -410,32 +389,27 @@ int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, con
 int do_eval(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
             void* lpost, void* grad) {
     if (pl.mode == lr::MODE_STEPWISE) return do_eval_stepwise(m, pl, st, C, beta, ll, lprior, lpost, grad);
-    LR_DISPATCH_TP(m, do_eval_t, m, pl, st, C, beta, ll, lprior, lpost, grad);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_eval_t, m, pl, st, C, beta, ll, lprior, lpost, grad)
+    return bad_width(m);
 }
-
-#define LR_DISPATCH_STEP(m, FN, ...)                                                     \
-    do {                                                                                 \
-        if ((m)->dtype == LR_F32 && (m)->P == 64) return FN<float, 64>(__VA_ARGS__);     \
-        if ((m)->dtype == LR_F32 && (m)->P == 128) return FN<float, 128>(__VA_ARGS__);   \
-        if ((m)->dtype == LR_F64 && (m)->P == 64) return FN<double, 64>(__VA_ARGS__);    \
-        if ((m)->dtype == LR_F64 && (m)->P == 128) return FN<double, 128>(__VA_ARGS__);  \
-        LR_DISPATCH_TP(m, FN, __VA_ARGS__);                                              \
-    } while (0)
 
 int do_stepwise(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, void* state,
                 double* lp_state, void* out, uint32_t* accepts) {
-    LR_DISPATCH_STEP(m, do_stepwise_t, m, pl, st, rs, o, state, lp_state, out, accepts);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_stepwise_t, m, pl, st, rs, o, state, lp_state, out, accepts)
+    return bad_width(m);
 }
 
 int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
                      void* lpost, void* grad) {
-    LR_DISPATCH_STEP(m, do_eval_stepwise_t, m, pl, st, C, beta, ll, lprior, lpost, grad);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_eval_stepwise_t, m, pl, st, C, beta, ll, lprior, lpost, grad)
+    return bad_width(m);
 }
 
 int do_chain(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, void* state,
              double* lp_state, void* out, uint32_t* accepts) {
     if (pl.mode == lr::MODE_STEPWISE) return do_stepwise(m, pl, st, rs, o, state, lp_state, out, accepts);
-    LR_DISPATCH_TP(m, do_chain_t, m, pl, st, rs, o, state, lp_state, out, accepts);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_chain_t, m, pl, st, rs, o, state, lp_state, out, accepts)
+    return bad_width(m);
 }
 
 }  // namespace

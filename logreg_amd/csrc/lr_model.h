@@ -50,6 +50,20 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(LR_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));   \
     } while (0)
 
+// Template dispatch by run-time dtype and padded width, spelled once.  f<float | double>(...) by an LR_F32 / LR_F64 value:
+#define LR_BY_DTYPE(dtype, f, ...) ((dtype) == LR_F32 ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
+#define LR_BY_DTYPE_W(dtype, W, f, ...) ((dtype) == LR_F32 ? f<float, W>(__VA_ARGS__) : f<double, W>(__VA_ARGS__))
+// ... `return f<float | double, P>(...)` for a padded width P of the list WIDTHS, both dtypes; falls through on any other width.  The
+// list decides what is instantiated: LR_WIDTHS_FUSED for what exists for the fused kernels' widths only, LR_WIDTHS_ALL for every width.
+#define LR_WIDTHS_FUSED(X, ...) X(4, __VA_ARGS__) X(8, __VA_ARGS__) X(16, __VA_ARGS__) X(32, __VA_ARGS__)
+#define LR_WIDTHS_ALL(X, ...) LR_WIDTHS_FUSED(X, __VA_ARGS__) X(64, __VA_ARGS__) X(128, __VA_ARGS__)
+#define LR_WIDTH_CASE(W, dtype, f, ...) case W: return LR_BY_DTYPE_W(dtype, W, f, __VA_ARGS__);
+#define LR_RETURN_BY_DTYPE_WIDTH(WIDTHS, dtype, P, f, ...) \
+    switch (P) { WIDTHS(LR_WIDTH_CASE, dtype, f, __VA_ARGS__) }
+// ... and f<P>(...) by width alone, for the host functions that build operand images: the matrix-pipe widths of narrow models, the wide ones
+#define LR_BY_WIDTH_MX(P, f, ...) ((P) == 8 ? f<8>(__VA_ARGS__) : (P) == 16 ? f<16>(__VA_ARGS__) : f<32>(__VA_ARGS__))
+#define LR_BY_WIDTH_WIDE(P, f, ...) ((P) == 64 ? f<64>(__VA_ARGS__) : f<128>(__VA_ARGS__))
+
 const lr::InstTable* find_table(int dtype, int P) {
     const lr::InstTable* all[] = {lr_inst_table_f32_p4(),  lr_inst_table_f32_p8(), lr_inst_table_f32_p16(),
                                   lr_inst_table_f32_p32(), lr_inst_table_f64_p4(), lr_inst_table_f64_p8(),

@@ -8,6 +8,7 @@
 // LDS, the device-memory images the model carries).  tests/test_gpu_planner.py times AUTO against every forced alternative
 // at shapes on both sides of the table's boundaries and fails when AUTO is more than 10 % off the best.
 #pragma once
+#include "../../include/logreg_hip_nuts.h"  // LR_KIND_NUTS (plan_run)
 
 namespace {
 
@@ -106,7 +107,7 @@ template <int P> size_t mfma_lds_bytes_p(int64_t ntw, int S) {
 }
 size_t mfma_lds_bytes(const lr_model* m, int S) {
     const int64_t tiles = (m->n + 15) / 16, ntw = (tiles + S - 1) / S;
-    return m->P == 8 ? mfma_lds_bytes_p<8>(ntw, S) : (m->P == 16 ? mfma_lds_bytes_p<16>(ntw, S) : mfma_lds_bytes_p<32>(ntw, S));
+    return LR_BY_WIDTH_MX(m->P, mfma_lds_bytes_p, ntw, S);
 }
 // 160 KB less the kernel's static exchange buffers (red: 2 x S x 64 x P/4 floats, redv: S x 64 doubles)
 size_t mfma_lds_budget(const lr_model* m, int S = 4) { return 160 * 1024 - (size_t)128 * S * m->P - (size_t)512 * S; }
@@ -238,12 +239,28 @@ bool plan_mixed_hmc(const lr_model* m, int64_t C, Plan* out, int* whole = nullpt
 // (5) measured overrides of vector-ALU plans; (6) a second part for the remainder between exactly-filled chain counts.
 struct PlanReq {
     const lr_model* m;
-    int64_t C;       // chains to plan for
-    int group, mode; // the caller's request (0 / LR_MODE_AUTO: the planner's choice)
-    bool for_eval;   // lr_eval: no matrix-core / stepwise / two-part plans
-    int kind;        // LR_KIND_* of the run, -1 = not a run of a known family (lr_plan, lr_eval)
+    int64_t C;           // chains to plan for
+    int group, mode;     // the caller's request (0 / LR_MODE_AUTO: the planner's choice)
+    bool for_eval;       // lr_eval: no matrix-core / stepwise / two-part plans
+    int kind;            // LR_KIND_* of the run, -1 = not a run of a known family (lr_plan, lr_eval)
+    bool hmc_bf16;       // the run is HMC and its interior leapfrog gradients may use the bf16 matrix pipe (LR_PREC_AUTO / BF16)
+    bool exact_tail_ok;  // ... and need not (LR_PREC_AUTO): a remainder may run on the all-fp32 register kernels
     bool automatic() const { return mode == LR_MODE_AUTO && group == 0 && !for_eval; }
 };
+
+// the chain count every chain-count-dependent choice is made for (lr_run_opts.plan_chains: a shard plans as the whole run)
+int64_t plan_count(const lr_run_opts* o) { return o->plan_chains > 0 ? (int64_t)o->plan_chains : o->n_chains; }
+
+// The three requests the ABI makes.  lr_plan: a chain count alone.  lr_eval: a forced matrix-core / stepwise mode of a narrow model means
+// nothing to an evaluation and is read as the planner's choice.  A run: the one place that reads the precision policy.
+PlanReq plan_request(const lr_model* m, int64_t C, int group, int mode) { return PlanReq{m, C, group, mode, false, -1, false, false}; }
+PlanReq plan_request_eval(const lr_model* m, const lr_run_opts* o) {
+    const bool any = (o->mode == LR_MODE_MFMA || o->mode == LR_MODE_STEPWISE) && m->P <= 32;
+    return PlanReq{m, o->n_chains, any ? 0 : o->group, any ? LR_MODE_AUTO : o->mode, true, -1, false, false};
+}
+PlanReq plan_request(const lr_model* m, int kind, const lr_run_opts* o) {
+    return PlanReq{m, plan_count(o), o->group, o->mode, false, kind, kind == LR_KIND_HMC && o->precision != LR_PREC_FULL, o->precision == LR_PREC_AUTO};
+}
 
 // (2) wide models (32 < p <= 128): only the stepwise engine exists; its partial kernels are MFMA GEMMs over blocks of 64 / 128
 // chains x row slices (lr_wide_bf16.h; float64 models: lr_wide_f64.h).  One workgroup per CU -- the fewest row slices -- measured
@@ -468,20 +485,15 @@ void plan_second_part_mfma(const PlanReq& q, Plan* out) {
     }
 }
 
-// `hmc_bf16`: the run is HMC and its interior leapfrog gradients may use the bf16 matrix pipe (LR_PREC_AUTO / BF16)
-// `exact_tail_ok`: ... and need not (LR_PREC_AUTO): a remainder may run on the all-fp32 register kernels
-// `kind`: LR_KIND_* of the run, -1 = not a run of a known family (lr_plan, lr_eval)
-int make_plan(const lr_model* m, int64_t C, int group, int mode, Plan* out, bool for_eval = false, bool hmc_bf16 = false, int kind = -1,
-              bool exact_tail_ok = false) {
-    if (for_eval && (mode == LR_MODE_MFMA || mode == LR_MODE_STEPWISE) && m->P <= 32) { mode = LR_MODE_AUTO; group = 0; }
-    const PlanReq q{m, C, group, mode, for_eval, kind};
-    if (hmc_bf16 && q.automatic() && plan_mfma_hmc(m, C, out)) {
-        if (kind >= 0 && (exact_tail_ok || m->dtype != LR_F32)) plan_second_part_mfma(q, out);  // (float64: the tail's interior is reduced too)
+int make_plan(const PlanReq& q, Plan* out) {
+    const lr_model* m = q.m;
+    if (q.hmc_bf16 && q.automatic() && plan_mfma_hmc(m, q.C, out)) {
+        if (q.kind >= 0 && (q.exact_tail_ok || m->dtype != LR_F32)) plan_second_part_mfma(q, out);  // (float64: the tail's interior is reduced too)
         return LR_OK;
     }
     int mixed_whole = -1;
-    if (hmc_bf16 && q.automatic() && plan_mixed_hmc(m, C, out, &mixed_whole)) {
-        if (kind >= 0) plan_second_part(q, m->table->variants[mixed_whole], out, lr::MODE_MIXED);
+    if (q.hmc_bf16 && q.automatic() && plan_mixed_hmc(m, q.C, out, &mixed_whole)) {
+        if (q.kind >= 0) plan_second_part(q, m->table->variants[mixed_whole], out, lr::MODE_MIXED);
         return LR_OK;
     }
     if (m->P > 32) return plan_wide(q, out);
@@ -490,19 +502,19 @@ int make_plan(const lr_model* m, int64_t C, int group, int mode, Plan* out, bool
     //  n=500 p=20, HMC L=20, it/s, lds 16 | stepwise: 4096 chains 1.53 | 0.98e7, 16 384: 1.54 | 1.47e7; profiles/r5_f64_p32.txt)
     const bool f64_wide_fused = m->dtype == LR_F64 && m->P == 32;
     const bool prefer_stepwise = lds_rows_bytes(m) > kLdsBudget ||
-                                 (!f64_wide_fused && row_bytes > kPlanConst.lds_rows_prefer_stepwise_bytes && C >= kPlanConst.lds_rows_prefer_stepwise_chains);
-    if (!for_eval && (mode == LR_MODE_STEPWISE || (mode == LR_MODE_AUTO && group == 0 && prefer_stepwise))) {
+                                 (!f64_wide_fused && row_bytes > kPlanConst.lds_rows_prefer_stepwise_bytes && q.C >= kPlanConst.lds_rows_prefer_stepwise_chains);
+    if (!q.for_eval && (q.mode == LR_MODE_STEPWISE || (q.automatic() && prefer_stepwise))) {
         plan_tall(q, out);
         return LR_OK;
     }
     int best = pick_variant(q);
     if (best < 0)
         return fail(LR_ERR_UNSUPPORTED, "no kernel variant for dtype=%d p=%d (padded %d) n=%lld group=%d mode=%d",
-                    m->dtype, m->p, m->P, (long long)m->n, group, mode);
+                    m->dtype, m->p, m->P, (long long)m->n, q.group, q.mode);
     if (q.automatic() && measured_overrides(q, &best, out)) return LR_OK;
     const lr::Variant& v = m->table->variants[best];
     *out = Plan{v.mode, v.G, v.R, v.mode == lr::MODE_MIXED ? mixed_lds_bytes(m) : v.mode == lr::MODE_LDS ? lds_rows_bytes(m) : (v.mode == lr::MODE_MFMA && m->dtype != LR_F32) ? row_bytes : (v.mode == lr::MODE_MFMA && v.R == 0 ? mfma_lds_bytes(m, v.G) : 0)};
-    if (v.mode == lr::MODE_REG && q.automatic() && kind >= 0) plan_second_part(q, v, out);
+    if (v.mode == lr::MODE_REG && q.automatic() && q.kind >= 0) plan_second_part(q, v, out);
     return LR_OK;
 }
 
@@ -525,6 +537,11 @@ int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out) 
     if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
     *out = Plan{lr::MODE_LDS, 16, 0, bytes};
     return LR_OK;
+}
+
+// the plan of a run of `kind` (LR_KIND_*): every lr_run_*, lr_plan_run_info and tests/host/plan_harness.hip come through here
+int plan_run(const lr_model* m, int kind, const lr_run_opts* o, int max_depth, Plan* out) {
+    return kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, max_depth, out) : make_plan(plan_request(m, kind, o), out);
 }
 
 // `group` means different things per mode (include/logreg_hip.h): lanes per chain (REG / LDS / GLOBAL / AUTO on narrow models:

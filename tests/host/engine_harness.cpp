@@ -4,7 +4,8 @@
 // number: it checks that every path of the host engine -- model images of every kind, one- and two-part plans with their fork / join
 // events, the stepwise engines and their workspaces, two chain sets on two streams, statistics, the Hessian, every error return, a
 // failing allocation at every point of model creation -- touches only memory it owns, frees what it allocates, and waits only on
-// events it recorded.  The four accumulators of kept draws (lr_predict, lr_acf, lr_marg, lr_loo) and lr_psis go through the same: their
+// events it recorded.  lr_run_nuts goes wherever the other kernel families go (and is refused where lr_plan_run refuses it), and the staged
+// host-pointer path of a run, of lr_run_nuts and of lr_eval survives a failing allocation at each of its arrays.  The four accumulators of kept draws (lr_predict, lr_acf, lr_marg, lr_loo) and lr_psis go through the same: their
 // whole life from host and device buffers, input longer than one staging piece, every refused argument, a failing allocation at every
 // allocation of create, accumulate and result.
 //   engine_harness all        every scenario on one thread
@@ -13,6 +14,7 @@
 #include "logreg_hip_acf.h"
 #include "logreg_hip_loo.h"
 #include "logreg_hip_marginals.h"
+#include "logreg_hip_nuts.h"
 #include "logreg_hip_predict.h"
 
 #include <cmath>
@@ -77,6 +79,40 @@ struct Dev {  // a device buffer through the ABI's own allocator
     ~Dev() { if (p) lr_free(0, p); }
 };
 
+// NUTS on one model: host and device buffers, with and without samples, counters, depths and statistics.  A shape or a forced
+// (mode, group) the family has no kernel for is refused by every call, as lr_plan_run refuses it.
+static void run_nuts(lr_model* m, const Data& d, int64_t C, int dtype, void* stream, int mode, int group) {
+    const size_t es = dtype == LR_F32 ? 4 : 8;
+    const int D = LR_NUTS_MAX_DEPTH;  // (the depth lr_plan_run plans for: the two agree on what fits the LDS)
+    lr_run_opts o{};
+    o.n_chains = C; o.thin = 2; o.iters = 2; o.seed = 7; o.mode = mode; o.group = group;
+    int32_t mo, go, ro;
+    const int want = lr_plan_run(m, LR_KIND_NUTS, &o, &mo, &go, &ro) == LR_OK ? LR_OK : LR_ERR_UNSUPPORTED;
+    std::vector<unsigned char> state((size_t)C * d.p * es, 0), out((size_t)2 * C * d.p * es);
+    std::vector<lr_nuts_counters> cnt(C, lr_nuts_counters{});
+    std::vector<int8_t> depth((size_t)2 * C);
+    std::vector<double> vec(d.p, 1.0), hstats((size_t)2 * C * 2 * d.p, 0.0);
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, out.data(), cnt.data(), depth.data()) == want, "nuts host, every array (C=%lld)", (long long)C);
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, nullptr, nullptr, nullptr) == want, "nuts host, the state alone");
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, out.data(), nullptr, depth.data()) == want, "nuts host, no counters");
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, nullptr, cnt.data(), nullptr) == want, "nuts host, counters alone");
+    o.stats = hstats.data(); o.stats_batch = 1; o.stats_first = 0; o.stats_slots = 2;
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, nullptr, cnt.data(), nullptr) == want, "nuts host, statistics and counters");
+    o.iters = 0;
+    EXPECT(lr_run_nuts(m, state.data(), 0.01, D, vec.data(), &o, out.data(), cnt.data(), depth.data()) == want, "nuts host, no iterations");
+    o.iters = 2;
+    Dev dstate((size_t)C * d.p * es), dout((size_t)2 * C * d.p * es), dcnt((size_t)C * sizeof(lr_nuts_counters)), ddepth((size_t)2 * C), dstats((size_t)2 * C * 2 * d.p * 8);
+    EXPECT(dstate.p && dout.p && dcnt.p && ddepth.p && dstats.p, "device buffers");
+    o.on_device = 1; o.stream = stream; o.stats = (double*)dstats.p;
+    const long on0 = hipstub_launches_on(stream);
+    EXPECT(lr_run_nuts(m, dstate.p, 0.01, D, vec.data(), &o, dout.p, (lr_nuts_counters*)dcnt.p, (int8_t*)ddepth.p) == want, "nuts device, every array + statistics");
+    o.stats = nullptr;
+    EXPECT(lr_run_nuts(m, dstate.p, 0.01, D, vec.data(), &o, nullptr, nullptr, nullptr) == want, "nuts device, the state alone");
+    EXPECT(lr_run_nuts(m, dstate.p, 0.01, D, vec.data(), &o, nullptr, (lr_nuts_counters*)dcnt.p, (int8_t*)ddepth.p) == want, "nuts device, no samples kept");
+    EXPECT(hipstub_launches_on(stream) == on0 + (want == LR_OK ? 3 : 0), "nuts device: one launch per call, on the caller's stream");
+    EXPECT(lr_stream_sync(0, stream) == LR_OK, "sync");
+}
+
 // every kernel family on one model, host buffers and device buffers, with and without statistics
 static void run_all_kinds(lr_model* m, const Data& d, int64_t C, int dtype, void* stream, int precision, int mode = LR_MODE_AUTO, int group = 0) {
     const size_t es = dtype == LR_F32 ? 4 : 8;
@@ -105,6 +141,7 @@ static void run_all_kinds(lr_model* m, const Data& d, int64_t C, int dtype, void
     e.n_chains = C; e.mode = LR_MODE_AUTO;
     EXPECT(lr_eval(m, beta.data(), ll.data(), ll.data(), ll.data(), grad.data(), &e) == LR_OK, "eval");
     EXPECT(lr_eval(m, beta.data(), nullptr, nullptr, ll.data(), nullptr, &e) == LR_OK, "eval lpost only");
+    run_nuts(m, d, C, dtype, stream, mode, group);
 }
 
 static void scenario_models() {
@@ -265,6 +302,33 @@ static void scenario_errors() {
     EXPECT(lr_run_hmc(m, st.data(), 0.1, 2, vec.data(), &b, out.data(), acc.data()) == LR_ERR_INVALID, "stats_batch = 0");
     b.stats_batch = 1; b.stats_first = 2; b.iters = 1;
     EXPECT(lr_run_hmc(m, st.data(), 0.1, 2, vec.data(), &b, out.data(), acc.data()) == LR_ERR_INVALID, "statistics window overrun");
+    // lr_run_nuts: its own parameters first, then the options and arrays as every run, then what its one kernel family cannot do
+    std::vector<lr_nuts_counters> cnt(64, lr_nuts_counters{});
+    std::vector<int8_t> dep(64);
+    EXPECT(lr_run_nuts(nullptr, st.data(), 0.1, 3, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts NULL model");
+    EXPECT(lr_run_nuts(m, st.data(), 0.0, 3, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts eps = 0");
+    EXPECT(lr_run_nuts(m, st.data(), NAN, 3, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts eps NaN");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 0, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts max_depth = 0");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, LR_NUTS_MAX_DEPTH + 1, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts max_depth beyond the limit");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, nullptr, &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts NULL dmm");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, neg.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts dmm < 0");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), nullptr, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts NULL opts");
+    EXPECT(lr_run_nuts(m, nullptr, 0.1, 3, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts NULL state");
+    b = o; b.thin = 0;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts thin = 0");
+    b = o; b.group = 3;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts group 3");
+    b = o; b.stats = stats.data(); b.stats_batch = 1; b.stats_first = 2; b.stats_slots = 2;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_INVALID, "nuts statistics window overrun");
+    b = o; b.group = 8;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_UNSUPPORTED, "nuts on 8 lanes per chain");
+    b = o; b.mode = LR_MODE_STEPWISE;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_UNSUPPORTED, "nuts on the stepwise engine");
+    b = o; b.mode = LR_MODE_REG;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_UNSUPPORTED, "nuts with rows in registers");
+    b = o; b.iters = 0; b.mode = LR_MODE_REG;
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &b, out.data(), cnt.data(), dep.data()) == LR_ERR_UNSUPPORTED, "nuts: refused before 'nothing to do'");
+    EXPECT(lr_run_nuts(m, st.data(), 0.1, 3, vec.data(), &o, out.data(), cnt.data(), dep.data()) == LR_OK, "nuts, after all the refusals");
     lr_run_opts e{};
     e.n_chains = 64;
     EXPECT(lr_eval(m, nullptr, out.data(), nullptr, nullptr, nullptr, &e) == LR_ERR_INVALID, "eval NULL beta");
@@ -333,6 +397,51 @@ static void scenario_failing_allocations() {
             lr_model_destroy(m);
             EXPECT(hipstub_live_allocs() <= before - 1, "a failed run leaked past the model's destruction");
         }
+    }
+}
+
+// The host-pointer path of a run, of lr_run_nuts and of lr_eval stages one device buffer per array the caller gave and none for one left
+// out.  The k-th of them fails, for every k: LR_ERR_NOMEM, nothing leaked, and the same call works next time.
+static void scenario_failing_staged_allocations() {
+    const Data d = make_data(200, 8, 98);
+    const int64_t C = 96;
+    for (int dtype : {LR_F32, LR_F64}) {
+        lr_model* m = nullptr;
+        EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), dtype, 0, &m) == LR_OK, "create");
+        if (!m) continue;
+        const size_t es = dtype == LR_F32 ? 4 : 8;
+        std::vector<unsigned char> st((size_t)C * d.p * es, 0), out((size_t)2 * C * d.p * es), ll((size_t)3 * C * es), grad((size_t)C * d.p * es);
+        std::vector<double> lp(C, -INFINITY), vec(d.p, 1.0), stats((size_t)2 * C * 2 * d.p, 0.0);
+        std::vector<uint32_t> acc(C, 0);
+        std::vector<lr_nuts_counters> cnt(C, lr_nuts_counters{});
+        std::vector<int8_t> dep((size_t)2 * C);
+        lr_run_opts o{};
+        o.n_chains = C; o.thin = 1; o.iters = 2; o.mode = LR_MODE_AUTO;
+        lr_run_opts os = o;
+        os.stats = stats.data(); os.stats_batch = 1; os.stats_slots = 2;
+        struct Call { const char* what; long arrays; std::function<int()> run; };
+        const Call calls[] = {
+            {"mala, every array + statistics", 5, [&] { return lr_run_mala(m, st.data(), lp.data(), 1e-3, vec.data(), &os, out.data(), acc.data()); }},
+            {"hmc, the state alone", 1, [&] { return lr_run_hmc(m, st.data(), 0.01, 2, vec.data(), &o, nullptr, nullptr); }},
+            {"nuts, every array + statistics", 5, [&] { return lr_run_nuts(m, st.data(), 0.01, 3, vec.data(), &os, out.data(), cnt.data(), dep.data()); }},
+            {"nuts, the state and the depths", 2, [&] { return lr_run_nuts(m, st.data(), 0.01, 3, vec.data(), &o, nullptr, nullptr, dep.data()); }},
+            {"eval, every output", 5, [&] { return lr_eval(m, st.data(), ll.data(), ll.data() + C * es, ll.data() + 2 * C * es, grad.data(), &o); }},
+            {"eval, lpost alone", 2, [&] { return lr_eval(m, st.data(), nullptr, nullptr, ll.data(), nullptr, &o); }}};
+        for (const Call& c : calls) {
+            const long live0 = hipstub_live_allocs(), m0 = hipstub_mallocs();
+            EXPECT(c.run() == LR_OK, "%s", c.what);
+            const long made = hipstub_mallocs() - m0;
+            EXPECT(made == c.arrays && hipstub_live_allocs() == live0, "%s: %ld device buffers staged for %ld arrays, %ld left behind", c.what, made, c.arrays, hipstub_live_allocs() - live0);
+            for (long k = 1; k <= made; ++k) {
+                hipstub_fail_malloc_at(k);
+                const int rc = c.run();
+                hipstub_fail_malloc_at(-1);
+                EXPECT(rc == LR_ERR_NOMEM, "%s: allocation %ld of %ld fails: rc %d", c.what, k, made, rc);
+                EXPECT(hipstub_live_allocs() == live0, "%s: allocation %ld of %ld fails: %ld device buffers leaked", c.what, k, made, hipstub_live_allocs() - live0);
+                EXPECT(c.run() == LR_OK, "%s: the call works after a failed one", c.what);
+            }
+        }
+        lr_model_destroy(m);
     }
 }
 
@@ -783,6 +892,7 @@ int main(int argc, char** argv) {
         scenario_two_streams();
         scenario_errors();
         scenario_failing_allocations();
+        scenario_failing_staged_allocations();
         scenario_second_device();
         scenario_accumulators();
         scenario_accumulator_errors();

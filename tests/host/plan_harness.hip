@@ -74,7 +74,9 @@ int main(int argc, char** argv) {
         m.d_xblk1 = im.wide1 ? yes : nullptr;
         Plan pl{};
         int rc = check_group_for(&m, group, mode);
-        if (rc == LR_OK) rc = make_plan(&m, chains, group, mode, &pl, false, kind == LR_KIND_HMC && prec != LR_PREC_FULL, kind, prec == LR_PREC_AUTO);
+        lr_run_opts o{};
+        o.n_chains = chains; o.group = group; o.mode = mode; o.precision = prec;
+        if (rc == LR_OK) rc = plan_run(&m, kind, &o, LR_NUTS_MAX_DEPTH, &pl);  // as every lr_run_* plans
         if (rc != LR_OK) std::printf("ERR %d %s\n", rc, g_err);
         else {
             const InteriorPlan ip = plan_interior(&m, chains);

@@ -5,9 +5,11 @@ side slots, the fork / join events of two-part plans and every argument check --
 separately, -fsanitize=thread) and linked, with the library's own instantiation objects, against tests/host/hip_stub.cpp: the 31 HIP
 runtime calls the library makes, on the host heap, launches as validated no-ops.  tests/host/engine_harness.cpp then drives the C ABI:
 13 model shapes x 2 dtypes (every image kind) x all four kernel families x both precision policies, host and device buffers,
-statistics, planned shards, the Hessian, every forced (mode, group), two chain sets on two streams + a wide model on alternating
-streams, 40 error returns, a failing device allocation at EVERY allocation of model creation and of a run (LR_ERR_NOMEM, nothing
-leaked, the model still usable), and a model, its stream, buffers and runs on device 1 of two (what a rank > 0 of the multi-GPU job does:
+statistics, planned shards, the Hessian, every forced (mode, group), lr_run_nuts beside them everywhere (host and device buffers, with
+and without samples, counters, depths and statistics; refused exactly where lr_plan_run refuses it), two chain sets on two streams + a
+wide model on alternating streams, 60 error returns, a failing device allocation at EVERY allocation of model creation and of a run
+(LR_ERR_NOMEM, nothing leaked, the model still usable), at every array the host-pointer path of a run, of lr_run_nuts and of lr_eval
+stages (one device buffer per array given, none for one left out; LR_ERR_NOMEM, nothing leaked, the same call works next), and a model, its stream, buffers and runs on device 1 of two (what a rank > 0 of the multi-GPU job does:
 not one allocation, creation or launch may happen with device 0 current, none may touch another device's stream or event), and the four
 accumulators of kept draws with lr_psis (csrc/lr_accum.h: their whole life from host and device buffers in both dtypes, padded and not,
 host input one item longer than a staging piece, every refused argument, a failing allocation at every allocation of create,
