@@ -5,7 +5,8 @@
  * The reference's library scripts run NUTS with a diagonal metric and no warm-up:
  *     Python/fit-blackjax-nuts.py:101   blackjax.nuts(lpost, 1e-3, pre), pre = [10,1,1,1,1,1,5,1], 10 000 iterations
  *     Python/fit-numpyro.py:36-46       numpyro NUTS on the same model
- * lr_run_nuts replaces their sampler loop.  BlackJAX's `inverse_mass_matrix = pre` is this call's dmm = 1 / pre.
+ * lr_run_nuts replaces their sampler loop.  BlackJAX's `inverse_mass_matrix = pre` is this call's dmm = 1 / pre.  (The warm-up that
+ * finds eps and dmm -- fit-numpyro.py:44 `num_warmup=1000` -- is logreg_hip_adapt.h.)
  *
  * A header of its own: logreg_hip.h's symbol set is pinned by the test double of the whole ABI; the entry points below are bound
  * from their own table (logreg_amd/_lib.py NUTS_SYMBOLS).  Every convention of logreg_hip.h holds (status codes, lr_last_error,

@@ -155,6 +155,32 @@ COV_SYMBOLS = {
     "lr_cov_destroy": (None, [_vp]),
 }
 
+ADAPT_ITER_BASE = 1 << 62  # LR_ADAPT_ITER_BASE
+ADAPT_MAX_WINDOWS = 32  # LR_ADAPT_MAX_WINDOWS
+ADAPT_TRACE_COLS = 5  # LR_ADAPT_TRACE_COLS
+
+
+class AdaptOpts(C.Structure):  # lr_adapt_opts (include/logreg_hip_adapt.h)
+    _fields_ = [("W", C.c_int32), ("adapt_metric", C.c_int32), ("delta", C.c_double), ("eps0", C.c_double), ("dmm0", C.c_void_p),
+                ("gamma", C.c_double), ("t0", C.c_double), ("kappa", C.c_double), ("init_buffer", C.c_int32), ("term_buffer", C.c_int32),
+                ("base_window", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AdaptInfo(C.Structure):  # lr_adapt_info
+    _fields_ = [("iterations", C.c_int64), ("metric_skipped", C.c_int64), ("windows", C.c_int32), ("n_windows", C.c_int32)]
+
+
+# name -> (restype, argtypes); every symbol include/logreg_hip_adapt.h declares.  A table of its own like COV_SYMBOLS, bound on first use
+# (load_adapt)
+ADAPT_SYMBOLS = {
+    "lr_adapt_schedule": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "lr_adapt_create": (C.c_int, [_vp, _i64, C.POINTER(AdaptOpts), C.POINTER(_vp)]),
+    "lr_adapt_run": (C.c_int, [_vp, _vp, _i64, _i32, _op, _vp, _vp, _vp, _vp]),
+    "lr_adapt_result": (C.c_int, [_vp, _dp, _vp, C.POINTER(AdaptInfo)]),
+    "lr_adapt_trace": (C.c_int, [_vp, _vp, _vp]),
+    "lr_adapt_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _predict = None
@@ -162,6 +188,7 @@ _acf = None
 _marg = None
 _loo = None
 _cov = None
+_adapt = None
 
 
 def _bind(L, table, slot=None):
@@ -235,6 +262,16 @@ def bind_covariance(L):
 def load_covariance():
     """The library with the covariance entry points bound (the same liblogreg_hip.so as load())."""
     return bind_covariance(load())
+
+
+def bind_adapt(L):
+    """`L` (a loaded library handle) with the NUTS warm-up entry points bound; resolved once per handle."""
+    return _bind(L, ADAPT_SYMBOLS, "_adapt")
+
+
+def load_adapt():
+    """The library with the NUTS warm-up entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_adapt(load())
 
 
 def load():

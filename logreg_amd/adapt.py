@@ -1,0 +1,102 @@
+"""Warm-up for `nutsKernel`: Stan-style windowed adaptation of one step size and one diagonal metric, pooled over all chains, on the device.
+
+The reference's NumPyro script runs `MCMC(kernel, num_warmup=1000, ...)` (`Python/fit-numpyro.py:44`); `nuts_warmup` is that warm-up for the
+fused sampler (include/logreg_hip_adapt.h states the definition; kernels in csrc/lr_nuts.h and csrc/lr_adapt.h):
+
+    res = nuts_warmup(model.lpost, model.glp, init, num_warmup=1000)      # from eps = 1 and the unit metric
+    out = mcmc(res.state, res.kernel, thin=1, iters=1000)                 # res.kernel = nutsKernel(lpost, glp, res.eps, res.dmm, max_depth)
+
+Every iteration the mean acceptance statistic of all C chains drives one dual-averaging step of the shared step size, and in the slow
+windows the states of all chains enter one pooled variance per coordinate: 4096 chains give both with almost no noise.  The W iterations
+are enqueued back to back, with no host round trip.  The result depends on the chain count: a shard of a larger run (`mcmc_sharded`)
+adapts by itself; pooling across ranks is not built.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from types import SimpleNamespace
+
+import numpy as np
+
+from . import _lib
+from ._lib import AdaptInfo, AdaptOpts, RunOpts, check
+from .kernels import NUTS_COUNTERS, _model_of, nutsKernel
+
+TRACE_COLUMNS = ("eps", "accept_stat", "log_eps_bar", "window", "n")
+
+
+def adapt_schedule(num_warmup, init_buffer=0, term_buffer=0, base_window=0):
+    """-> (first iteration of the first window, [exclusive window ends]) of a warm-up of `num_warmup` iterations (`lr_adapt_schedule`:
+    host code, no device).  Buffers: 0 = Stan's defaults 75, 50, 25."""
+    L = _adapt_library()
+    ends = (C.c_int32 * _lib.ADAPT_MAX_WINDOWS)()
+    n, init = C.c_int32(), C.c_int32()
+    check(L.lr_adapt_schedule(int(num_warmup), int(init_buffer), int(term_buffer), int(base_window), ends, C.byref(n), C.byref(init)))
+    return int(init.value), [int(e) for e in ends[:n.value]]
+
+
+def _adapt_library(L=None):
+    L = _lib.load() if L is None else L
+    try:
+        return _lib.bind_adapt(L)
+    except AttributeError as e:
+        raise _lib.LogregHipError(f"this library has no warm-up entry points (include/logreg_hip_adapt.h): {e}") from e
+
+
+def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
+                chain_offset=0, keep=False):
+    """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
+
+    Returns an object with `eps`, `dmm`, `pre` (= 1 / dmm: BlackJAX's inverse mass matrix), `state` `[C, p]`, `kernel`
+    (`nutsKernel(lpost, glp, eps, dmm, max_depth)`, ready for `mcmc`), `trace` `[W, 5]` (columns `TRACE_COLUMNS`), `metric_trace`
+    `[windows, 2, p]` (var, dmm per window), `info` (the per-chain counters as `ChainSet.nuts_info` gives them, and `metric_skipped`,
+    `windows`, `seed`) and, with `keep=True`, `draws` `[W, C, p]`.  `lpost` and `glp` must be the closures of one `LogReg`."""
+    model = _model_of(lpost, "lpost")
+    if model is None or _model_of(glp, "glp") is not model:
+        raise ValueError("nuts_warmup needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)")
+    W, max_depth = int(num_warmup), int(max_depth)
+    if W < 1:
+        raise ValueError(f"num_warmup must be >= 1, got {num_warmup}")
+    if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
+        raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
+    if not 0.0 < float(target_accept) < 1.0:
+        raise ValueError(f"target_accept must be in (0, 1), got {target_accept}")
+    if not (np.isfinite(eps) and float(eps) > 0):
+        raise ValueError(f"eps must be finite and > 0, got {eps}")
+    dmm0 = np.ascontiguousarray(np.broadcast_to(np.asarray(dmm, dtype=np.float64), (model.p,)))
+    if not np.all(np.isfinite(dmm0) & (dmm0 > 0)):
+        raise ValueError("dmm must be finite and > 0")
+    st = np.array(np.atleast_2d(np.asarray(init, dtype=np.float64)), dtype=model.np_dtype, order="C")
+    if st.ndim != 2 or st.shape[1] != model.p:
+        raise ValueError(f"init must be [p] or [C,p] with p={model.p}; got {np.shape(init)}")
+    Cn = st.shape[0]
+    L = _adapt_library(model._L)  # the library that made the model
+    _lib.require_gpu()
+    if seed is None:
+        seed = int(np.random.randint(0, 2**31 - 1))
+    o = AdaptOpts(W=W, adapt_metric=int(bool(adapt_metric)), delta=float(target_accept), eps0=float(eps), dmm0=dmm0.ctypes.data)
+    h = C.c_void_p()
+    check(L.lr_adapt_create(model.handle, Cn, C.byref(o), C.byref(h)))
+    try:
+        counters = np.zeros(Cn, dtype=NUTS_COUNTERS)
+        draws = np.empty((W, Cn, model.p), dtype=model.np_dtype) if keep else None
+        opts = RunOpts(n_chains=Cn, chain_offset=int(chain_offset), thin=1, iters=1, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO,
+                       on_device=0)
+        check(L.lr_adapt_run(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
+        e, info = C.c_double(), AdaptInfo()
+        dm = np.empty(model.p, dtype=np.float64)
+        check(L.lr_adapt_result(h, C.byref(e), dm.ctypes.data, C.byref(info)))
+        trace = np.zeros((W, _lib.ADAPT_TRACE_COLS), dtype=np.float64)
+        metric = np.zeros((info.n_windows, 2, model.p), dtype=np.float64)
+        check(L.lr_adapt_trace(h, trace.ctypes.data, metric.ctypes.data if info.n_windows else None))
+    finally:
+        L.lr_adapt_destroy(h)
+    res = SimpleNamespace(eps=float(e.value), dmm=dm, pre=1.0 / dm, state=st.astype(np.float64), trace=trace, metric_trace=metric,
+                          kernel=nutsKernel(lpost, glp, float(e.value), dm, max_depth),
+                          info={"n_leapfrog": counters["n_leapfrog"].astype(np.int64), "divergent": counters["divergent"].astype(np.int64),
+                                "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
+                                "mean_accept_stat": counters["accept_stat_sum"] / W, "metric_skipped": int(info.metric_skipped),
+                                "windows": int(info.windows), "iterations": int(info.iterations), "seed": int(seed)})
+    if keep:
+        res.draws = draws
+    return res

@@ -4,6 +4,7 @@
 //   lr_plan.h    which kernel variant runs a request (data): PlanReq is built by plan_request*(), planned by make_plan() / plan_run()
 //   lr_engine.h  kernel argument packing, workspaces, the stepwise driver   lr_inst*.hip the launches, one unit per (dtype, width)
 //   lr_accum.h   the scaffold of the accumulators of kept draws (the second half of this file, from the `posterior prediction` divider)
+//   lr_adapt.h   the kernels of the NUTS warm-up (include/logreg_hip_adapt.h; its host side is the `NUTS warm-up` divider below)
 // The first half has one of each: check_opts() for the options of every call, run_request() for the front every lr_run_* shares (check,
 // plan_run(), nothing to do, device buffers or staged()), staged() for every call made with host pointers (run, NUTS, eval: allocate
 // what the call uses, copy in, launch on the NULL stream, the only hipDeviceSynchronize of the run path, copy back), and in
@@ -17,6 +18,7 @@
 #include "../../include/logreg_hip_marginals.h"
 #include "../../include/logreg_hip_loo.h"
 #include "../../include/logreg_hip_cov.h"
+#include "../../include/logreg_hip_adapt.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -36,6 +38,7 @@
 #include "lr_cov.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
+#include "lr_adapt.h"
 #include "lr_hessian.h"
 #include "lr_mfma.h"
 #include "lr_predict.h"
@@ -1210,6 +1213,269 @@ void lr_cov_destroy(lr_cov* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     free_all({h->d_state, h->in.p, h->ws.p});
+    delete h;
+}
+
+// ---- NUTS warm-up: pooled step-size and metric adaptation (include/logreg_hip_adapt.h; kernels: lr_nuts.h TUNED, lr_adapt.h) ---------------
+}  // extern "C"
+struct lr_adapt {
+    lr_model* m = nullptr;
+    int64_t C = 0, B = 0;  // chains, workgroups of k_adapt_partial
+    int W = 0, n_windows = 0, init = 0;
+    int ends[LR_ADAPT_MAX_WINDOWS] = {};
+    double delta = 0.8, gamma = 0.05, t0 = 10.0, kappa = 0.75;
+    int64_t t = 0;     // iterations enqueued
+    int m_since = 0;   // ... of them since the last restart of dual averaging
+    int window = 0;    // the first window that has not ended
+    hipStream_t last = nullptr;  // stream of the last run call: results follow it
+    bool failed = false;         // a launch failed part-way through a run call: what is enqueued no longer matches the counts above
+    // one device block: da | dmm [p] | window triple [1 + 2 p] | partials [B][2 + 2 P] | trace [W][5] | metric [windows][2][p] | astat [C] | NutsTune
+    double* d_fixed = nullptr;
+    size_t words = 0, tune_bytes = 0;
+    Workspace st_state, st_out, st_tally, st_depth, st_astat;  // a call made with host pointers stages its arrays here
+    int p() const { return m->p; }
+    size_t o_dmm() const { return 8; }
+    size_t o_win() const { return o_dmm() + (size_t)p(); }
+    size_t o_partial() const { return o_win() + 1 + 2 * (size_t)p(); }
+    size_t o_trace() const { return o_partial() + (size_t)B * lr::adapt_partial_words(m->P); }
+    size_t o_metric() const { return o_trace() + (size_t)W * LR_ADAPT_TRACE_COLS; }
+    size_t o_astat() const { return o_metric() + (size_t)(n_windows > 0 ? n_windows : 1) * 2 * p(); }
+    size_t o_tune() const { return o_astat() + (size_t)C; }
+    lr::AdaptDev dev() const { return lr::AdaptDev{d_fixed, d_fixed + o_dmm(), d_fixed + o_win(), d_fixed + o_partial(), d_fixed + o_trace(), d_fixed + o_metric()}; }
+    double* astat() const { return d_fixed + o_astat(); }
+    void* tune() const { return d_fixed + o_tune(); }
+};
+namespace {
+static_assert(LR_ADAPT_TRACE_COLS == lr::kAdaptTraceCols && lr::AD_SLOTS <= 8, "logreg_hip_adapt.h and lr_adapt.h");
+static_assert(LR_ADAPT_WIDTH(3) == 4 && LR_ADAPT_WIDTH(8) == 8 && LR_ADAPT_WIDTH(9) == 16 && LR_ADAPT_WIDTH(20) == 32, "the fused kernels' padded widths");
+
+// the schedule of include/logreg_hip_adapt.h; buffers already defaulted
+int adapt_windows(int W, int init, int term, int base, int* ends, int* init_out) {
+    int n = 0;
+    if (W >= 20) {
+        if ((int64_t)init + base + term > W) {
+            init = (int)(0.15 * W);
+            term = (int)(0.10 * W);
+            base = W - init - term;
+        }
+        int64_t start = init, size = base;
+        while (start < W - term && n < LR_ADAPT_MAX_WINDOWS && size > 0) {
+            int64_t end = start + size;
+            if (end + 2 * size > W - term) end = W - term;
+            ends[n++] = (int)end;
+            start = end;
+            size *= 2;
+        }
+    }
+    if (init_out) *init_out = n ? init : W;
+    return n;
+}
+
+// the NutsTune block of (eps, dmm), formed as do_nuts_t forms NutsArgs
+template <typename T, int P>
+int adapt_tune_image(int p, double eps, const double* dmm, std::vector<unsigned char>* img) {
+    lr::NutsTune<T, P> t{};
+    t.step = (T)eps;
+    for (int j = 0; j < P; ++j) {
+        t.a[j] = j < p ? (T)std::sqrt(dmm[j]) : T(0);
+        t.b[j] = j < p ? (T)(eps / dmm[j]) : T(0);
+        t.c[j] = j < p ? (T)(1.0 / dmm[j]) : T(0);
+    }
+    img->resize(sizeof(t));
+    std::memcpy(img->data(), &t, sizeof(t));
+    return LR_OK;
+}
+
+// `iters` iterations, three launches each, on `st`; every pointer is device memory
+template <typename T, int P>
+int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
+                  int8_t* depth_out, double* astat_out, int64_t iters) {
+    lr_model* m = h->m;
+    auto ma = model_args<T, P>(m);
+    const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const lr::AdaptDev dev = h->dev();
+    auto* tune = static_cast<lr::NutsTune<T, P>*>(h->tune());
+    const size_t row = (size_t)h->C * m->p;
+    h->last = st;
+    for (int64_t i = 0; i < iters; ++i) {
+        lr::NutsTunedArgs<T, P> na{};
+        na.state = static_cast<T*>(state);
+        na.out = out ? static_cast<T*>(out) + (size_t)i * row : nullptr;
+        na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
+        na.depth_out = depth_out ? depth_out + (size_t)i * h->C : nullptr;
+        na.C = h->C;
+        na.chain_offset = o->chain_offset;
+        na.iters = 1;
+        na.thin = 1;
+        na.iter_offset = LR_ADAPT_ITER_BASE + h->t;
+        na.seed = o->seed;
+        na.p = m->p;
+        na.max_depth = max_depth;
+        na.stats = lr::StatsArgs{nullptr, 1, 0};
+        na.tune = tune;
+        na.astat = astat_out ? astat_out + (size_t)i * h->C : h->astat();
+        const int rc = m->table->launch_nuts_tuned(&cfg, h->C, &ma, &na);
+        if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "lr_adapt_run: NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+        const bool in_window = h->window < h->n_windows && h->t >= (h->window ? h->ends[h->window - 1] : h->init);
+        const bool window_end = in_window && h->t == h->ends[h->window] - 1;
+        hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), na.astat, h->C, m->p, in_window ? 1 : 0,
+                           dev.partial);
+        LR_HIP(hipGetLastError());
+        const lr::AdaptStep s{h->C, h->t, m->p, h->m_since + 1, in_window ? h->window : -1, window_end ? 1 : 0, h->t == h->W - 1 ? 1 : 0, h->delta, h->gamma, h->t0, h->kappa};
+        hipLaunchKernelGGL((lr::k_adapt_update<T, P>), dim3(1), dim3(64), 0, st, dev, s, tune);
+        LR_HIP(hipGetLastError());
+        ++h->t;
+        h->m_since = window_end ? 0 : h->m_since + 1;
+        if (window_end) ++h->window;
+    }
+    return LR_OK;
+}
+int adapt_enqueue_any(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
+                      int8_t* depth_out, double* astat_out, int64_t iters) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, h->m->dtype, h->m->P, adapt_enqueue, h, pl, st, o, max_depth, state, out, counters, depth_out, astat_out, iters)
+    return bad_width(h->m);
+}
+// ... and a failure of it ends the handle's use: an iteration may be enqueued without its update, so the tuning block and the trace no
+// longer belong together (lr_adapt_run refuses the handle from then on; result and trace still read what is there)
+int adapt_enqueue_checked(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
+                          int8_t* depth_out, double* astat_out, int64_t iters) {
+    const int rc = adapt_enqueue_any(h, pl, st, o, max_depth, state, out, counters, depth_out, astat_out, iters);
+    if (rc != LR_OK) h->failed = true;
+    return rc;
+}
+int adapt_tune_image_any(const lr_model* m, double eps, const double* dmm, std::vector<unsigned char>* img) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, adapt_tune_image, m->p, eps, dmm, img)
+    return bad_width(m);
+}
+}  // namespace
+extern "C" {
+
+int lr_adapt_schedule(int32_t W, int32_t init_buffer, int32_t term_buffer, int32_t base_window, int32_t* ends, int32_t* n_windows, int32_t* init_out) {
+    if (!ends || !n_windows) return fail(LR_ERR_INVALID, "lr_adapt_schedule: ends / n_windows is NULL");
+    if (W < 1) return fail(LR_ERR_INVALID, "lr_adapt_schedule: W must be >= 1 (got %d)", W);
+    if (init_buffer < 0 || term_buffer < 0 || base_window < 0)
+        return fail(LR_ERR_INVALID, "lr_adapt_schedule: the buffers must be >= 0, 0 for the default (got %d, %d, %d)", init_buffer, term_buffer, base_window);
+    *n_windows = adapt_windows(W, init_buffer ? init_buffer : 75, term_buffer ? term_buffer : 50, base_window ? base_window : 25, ends, init_out);
+    return LR_OK;
+}
+
+int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** out) {
+    if (!m || !o || !out) return fail(LR_ERR_INVALID, "lr_adapt_create: model / opts / out is NULL");
+    if (C <= 0) return fail(LR_ERR_INVALID, "lr_adapt_create: C must be positive (got %lld)", (long long)C);
+    if (C > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_adapt_create: %lld chains are beyond the launch grid", (long long)C);
+    if (o->W < 1) return fail(LR_ERR_INVALID, "lr_adapt_create: W must be >= 1 (got %d)", o->W);
+    if (o->init_buffer < 0 || o->term_buffer < 0 || o->base_window < 0)
+        return fail(LR_ERR_INVALID, "lr_adapt_create: the buffers must be >= 0, 0 for the default (got %d, %d, %d)", o->init_buffer, o->term_buffer, o->base_window);
+    if (!(o->delta >= 0 && o->delta < 1)) return fail(LR_ERR_INVALID, "lr_adapt_create: delta must be in (0, 1), 0 for the default 0.8 (got %g)", o->delta);
+    if (!(o->eps0 >= 0) || !std::isfinite(o->eps0)) return fail(LR_ERR_INVALID, "lr_adapt_create: eps0 must be finite and > 0, 0 for the default 1 (got %g)", o->eps0);
+    for (const double v : {o->gamma, o->t0, o->kappa})
+        if (!(v >= 0) || !std::isfinite(v)) return fail(LR_ERR_INVALID, "lr_adapt_create: gamma, t0 and kappa must be finite and > 0, 0 for the defaults (got %g)", v);
+    if (o->dmm0)
+        if (const int rc = positive_vec("lr_adapt_create: dmm0", o->dmm0, m->p)) return rc;
+    if (m->P > 32 || !m->table || !m->table->launch_nuts_tuned)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
+    if (const int rc = use_device(m->device, "lr_adapt_create")) return rc;
+    std::unique_ptr<lr_adapt> h(new lr_adapt());
+    h->m = m;
+    h->C = C;
+    h->B = (C + lr::kAdaptBlock - 1) / lr::kAdaptBlock;
+    h->W = o->W;
+    h->delta = o->delta > 0 ? o->delta : 0.8;
+    h->gamma = o->gamma > 0 ? o->gamma : 0.05;
+    h->t0 = o->t0 > 0 ? o->t0 : 10.0;
+    h->kappa = o->kappa > 0 ? o->kappa : 0.75;
+    h->n_windows = adapt_windows(o->W, o->init_buffer ? o->init_buffer : 75, o->term_buffer ? o->term_buffer : 50, o->base_window ? o->base_window : 25, h->ends, &h->init);
+    if (!o->adapt_metric) h->n_windows = 0;
+    const double eps0 = o->eps0 > 0 ? o->eps0 : 1.0;
+    std::vector<double> dmm((size_t)m->p, 1.0);
+    if (o->dmm0) std::copy(o->dmm0, o->dmm0 + m->p, dmm.begin());
+    std::vector<unsigned char> tune;
+    if (const int rc = adapt_tune_image_any(m, eps0, dmm.data(), &tune)) return rc;
+    h->tune_bytes = tune.size();
+    h->words = h->o_tune();
+    const size_t want = h->words * sizeof(double) + h->tune_bytes;
+    if (hipMalloc((void**)&h->d_fixed, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_adapt_create: allocating %zu bytes of state failed", want);
+    std::vector<double> img(h->words, 0.0);
+    img[lr::AD_MU] = std::log(10.0 * eps0);
+    img[lr::AD_EPS] = img[lr::AD_EPS_REPORT] = eps0;
+    std::copy(dmm.begin(), dmm.end(), img.begin() + h->o_dmm());
+    hipError_t e = hipMemcpy(h->d_fixed, img.data(), h->words * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->tune(), tune.data(), tune.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        lr_adapt_destroy(h.release());
+        return fail(LR_ERR_HIP, "lr_adapt_create: copying the start state failed: %s", hipGetErrorString(e));
+    }
+    *out = h.release();
+    return LR_OK;
+}
+
+int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters, int8_t* depth_out,
+                 double* astat_out) {
+    if (!h || !state || !o) return fail(LR_ERR_INVALID, "lr_adapt_run: handle / state / opts is NULL");
+    if (h->failed) return fail(LR_ERR_HIP, "lr_adapt_run: a launch of an earlier call failed; this warm-up cannot go on (destroy the handle and start again)");
+    if (iters < 0 || iters > h->W - h->t)
+        return fail(LR_ERR_INVALID, "lr_adapt_run: iters must be in 0..%lld, the iterations that remain of W = %d (got %lld)", (long long)(h->W - h->t), h->W, (long long)iters);
+    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "lr_adapt_run: max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
+    if (o->n_chains != h->C) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->n_chains must be the handle's %lld chains (got %lld)", (long long)h->C, (long long)o->n_chains);
+    if (o->stats) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->stats must be NULL (a warm-up keeps no streaming statistics)");
+    lr_run_opts oo = *o;  // iters, thin and iter_offset are the warm-up's own
+    oo.iters = 1;
+    oo.thin = 1;
+    oo.iter_offset = 0;
+    lr_model* m = h->m;
+    if (const int rc = check_opts(m, &oo, true)) return rc;
+    LR_HIP(hipSetDevice(m->device));
+    Plan pl;
+    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl)) return rc;
+    if (iters == 0) return LR_OK;
+    if (oo.on_device) return adapt_enqueue_checked(h, pl, (hipStream_t)oo.stream, &oo, max_depth, state, out, counters, depth_out, astat_out, iters);
+    const size_t C = (size_t)h->C, sbytes = C * m->p * m->esize();
+    struct { Workspace* ws; void* host; size_t bytes; bool in; const char* what; } const b[] = {
+        {&h->st_state, state, sbytes, true, "staged state"},
+        {&h->st_out, out, (size_t)iters * sbytes, false, "staged draws"},
+        {&h->st_tally, counters, C * sizeof(lr_nuts_counters), true, "staged counters"},
+        {&h->st_depth, depth_out, (size_t)iters * C, false, "staged depths"},
+        {&h->st_astat, astat_out, (size_t)iters * C * sizeof(double), false, "staged acceptance statistics"}};
+    for (const auto& q : b)
+        if (q.host)
+            if (const int rc = q.ws->grow(q.bytes, "lr_adapt_run", q.what)) return rc;
+    for (const auto& q : b)
+        if (q.host && q.in) LR_HIP(hipMemcpy(q.ws->p, q.host, q.bytes, hipMemcpyHostToDevice));
+    auto dp = [&](int i) { return b[i].host ? b[i].ws->p : nullptr; };
+    if (const int rc = adapt_enqueue_checked(h, pl, nullptr, &oo, max_depth, dp(0), dp(1), static_cast<lr_nuts_counters*>(dp(2)), static_cast<int8_t*>(dp(3)),
+                                         static_cast<double*>(dp(4)), iters))
+        return rc;
+    LR_HIP(hipStreamSynchronize(nullptr));
+    for (const auto& q : b)
+        if (q.host) LR_HIP(hipMemcpy(q.host, q.ws->p, q.bytes, hipMemcpyDeviceToHost));
+    return LR_OK;
+}
+
+int lr_adapt_result(lr_adapt* h, double* eps, double* dmm, lr_adapt_info* info) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_result: handle is NULL");
+    LR_HIP(hipSetDevice(h->m->device));
+    LR_HIP(hipStreamSynchronize(h->last));
+    double da[8];
+    LR_HIP(hipMemcpy(da, h->d_fixed, sizeof(da), hipMemcpyDeviceToHost));
+    if (eps) *eps = da[lr::AD_EPS_REPORT];
+    if (dmm) LR_HIP(hipMemcpy(dmm, h->d_fixed + h->o_dmm(), (size_t)h->p() * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) *info = lr_adapt_info{h->t, (int64_t)da[lr::AD_SKIPPED], (int32_t)da[lr::AD_WINDOWS], h->n_windows};
+    return LR_OK;
+}
+
+int lr_adapt_trace(lr_adapt* h, double* trace, double* metric) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_trace: handle is NULL");
+    LR_HIP(hipSetDevice(h->m->device));
+    LR_HIP(hipStreamSynchronize(h->last));
+    if (trace) LR_HIP(hipMemcpy(trace, h->d_fixed + h->o_trace(), (size_t)h->W * LR_ADAPT_TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (metric && h->n_windows > 0) LR_HIP(hipMemcpy(metric, h->d_fixed + h->o_metric(), (size_t)h->n_windows * 2 * h->p() * sizeof(double), hipMemcpyDeviceToHost));
+    return LR_OK;
+}
+
+void lr_adapt_destroy(lr_adapt* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->m->device);
+    free_all({h->d_fixed, h->st_state.p, h->st_out.p, h->st_tally.p, h->st_depth.p, h->st_astat.p});
     delete h;
 }
 

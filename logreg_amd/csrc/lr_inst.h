@@ -73,6 +73,8 @@ struct InstTable {
     int (*launch_mfma_image)(hipStream_t, const void* rows, int64_t n, void* store);
     // NUTS (lr_nuts.h), rows in LDS on 16 lanes per chain; `nuts_args` is a NutsArgs<T,P>; null where no such kernel exists
     int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
+    // ... and its TUNED instantiation, step and metric from a device block (the warm-up, lr_adapt.h); `nuts_args` is a NutsTunedArgs<T,P>
+    int (*launch_nuts_tuned)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
 };
 
 }  // namespace lr

@@ -16,6 +16,8 @@
 // LDS after the rows: 2 x max_depth x P / 16 values per lane -- in registers they would go to scratch, which the build refuses.
 #pragma once
 
+#include <type_traits>
+
 #include "lr_kernels.h"
 
 namespace lr {
@@ -44,6 +46,19 @@ template <typename T, int P> struct NutsArgs {
     StatsArgs stats;
 };
 
+// The tuning of NutsArgs (step, a, b, c) as a block in device memory, and the arguments of the TUNED instantiation of k_nuts, which reads
+// it from there: the warm-up (include/logreg_hip_adapt.h, lr_adapt.h) rewrites the block between the launches of consecutive iterations
+// and reads `astat` [C], the acceptance statistic of the launch's last iteration.  NutsArgs keeps its layout.
+template <typename T, int P> struct NutsTune {
+    T step;
+    T a[P], b[P], c[P];
+};
+template <typename T, int P> struct NutsTunedArgs : NutsArgs<T, P> {
+    const NutsTune<T, P>* tune;
+    double* astat;
+};
+template <typename T, int P, bool TUNED> using NutsArgsOf = std::conditional_t<TUNED, NutsTunedArgs<T, P>, NutsArgs<T, P>>;
+
 // dynamic LDS of k_nuts beyond the rows: the checkpoints of a 256-lane workgroup
 template <typename T, int P> constexpr size_t nuts_ckpt_bytes(int max_depth) { return (size_t)2 * max_depth * ((P + 15) / 16) * 256 * sizeof(T); }
 
@@ -62,8 +77,8 @@ __device__ __forceinline__ double nuts_lae(double a, double b) {  // log(exp(a) 
     return mx + log1p(exp(d));
 }
 
-template <typename T, int P, int MODE, int R>
-__global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgs<T, P> a) {
+template <typename T, int P, int MODE, int R, bool TUNED = false>
+__global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P, TUNED> a) {
     static_assert(MODE == MODE_LDS, "rows in LDS");
     constexpr int G = 16, NK = (P + 15) / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -81,9 +96,15 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgs<T, P> 
     for (int k = 0; k < NK; ++k) {
         const int j = r + 16 * k, js = j < P ? j : 0;
         x[k] = j < a.p ? a.state[chain * a.p + j] : T(0);
-        ca[k] = j < P ? a.a[js] : T(0);
-        cb[k] = j < P ? a.b[js] : T(0);
-        cc[k] = j < P ? a.c[js] : T(0);
+        if constexpr (TUNED) {
+            ca[k] = j < P ? a.tune->a[js] : T(0);
+            cb[k] = j < P ? a.tune->b[js] : T(0);
+            cc[k] = j < P ? a.tune->c[js] : T(0);
+        } else {
+            ca[k] = j < P ? a.a[js] : T(0);
+            cb[k] = j < P ? a.b[js] : T(0);
+            cc[k] = j < P ? a.c[js] : T(0);
+        }
         civ[k] = j < P ? m.prior.inv_var[js] : T(0);
     }
     const double lprior_const = m.prior.lprior_const;
@@ -148,7 +169,11 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgs<T, P> 
     uint32_t n_div = 0, n_hit = 0;
     const int md = a.max_depth;
     const int nsteps = (1 << md) - 1;
-    const T heps = T(0.5) * a.step;
+    T step;
+    if constexpr (TUNED) step = a.tune->step;
+    else step = a.step;
+    const T heps = T(0.5) * step;
+    [[maybe_unused]] double last_stat = 0.0;  // (TUNED) the acceptance statistic of the last iteration
     const int rz = r < P ? r : 0;  // lanes beyond the padded width read coordinate 0's normal (times a zero scale)
 
     DrawBatch<T, P, G> draws;
@@ -315,7 +340,9 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgs<T, P> 
             const bool hit = !div && !turned && depth == md;
             n_leap += (uint64_t)nleaf;
             depth_sum += (uint64_t)depth;
-            acc_sum += sumacc / (double)(nleaf > 0 ? nleaf : 1);
+            const double stat = sumacc / (double)(nleaf > 0 ? nleaf : 1);
+            acc_sum += stat;
+            if constexpr (TUNED) last_stat = stat;
             n_div += div ? 1u : 0u;
             n_hit += hit ? 1u : 0u;
             depth_signed = div ? -depth : depth;
@@ -354,6 +381,8 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgs<T, P> 
             cn->divergent += n_div;
             cn->max_depth_hits += n_hit;
         }
+        if constexpr (TUNED)
+            if (r == 0) a.astat[chain] = last_stat;
     }
 }
 
