@@ -20,15 +20,15 @@ from .data import load_pima, load_pima_parquet, synthetic_logreg  # noqa: F401
 from .diagnostics import describe, ess_geyer, ess_per_param, ess_pooled, split_rhat, summarise  # noqa: F401
 from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKernel, nutsKernel, rwProposal,  # noqa: F401
                       ulKernel)
-from .adapt import nuts_warmup  # noqa: F401
+from .adapt import nuts_warmup, nuts_warmup_dense  # noqa: F401
 from .model import DeviceArray, LogReg  # noqa: F401
-from .optimize import find_map, overdispersed_init  # noqa: F401
+from .optimize import find_map, laplace_metric, overdispersed_init  # noqa: F401
 from .predict import PosteriorPredictive, merge_predictive, predict_proba, waic, waic_from_table  # noqa: F401
 from .loo import PsisLoo, loo_compare, loo_from_table, psis_from_loglik, psis_loo  # noqa: F401
 from .output import print_summary, read_parquet, to_frame, write_parquet  # noqa: F401
 
 __all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "malaKernel", "hmcKernel", "ulKernel", "nutsKernel",
            "rwProposal", "mcmc", "load_pima", "load_pima_parquet", "synthetic_logreg", "summarise", "describe",
-           "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "overdispersed_init", "write_parquet",
+           "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "laplace_metric", "overdispersed_init", "write_parquet",
            "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals", "Covariance", "covariance_scaling", "merge_covariance",
-           "nuts_warmup", "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare"]
+           "nuts_warmup", "nuts_warmup_dense", "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare"]

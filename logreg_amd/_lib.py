@@ -181,8 +181,22 @@ ADAPT_SYMBOLS = {
     "lr_adapt_destroy": (None, [_vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/logreg_hip_dense.h declares.  A table of its own like ADAPT_SYMBOLS, bound on first use
+# (load_dense)
+DENSE_SYMBOLS = {
+    "lr_dense_factor": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
+    "lr_run_nuts_dense": (C.c_int, [_vp, _vp, C.c_double, _i32, _vp, _op, _vp, _vp, _vp]),
+    "lr_dense_adapt_create": (C.c_int, [_vp, _i64, C.POINTER(AdaptOpts), _vp, C.POINTER(_vp)]),
+    "lr_dense_adapt_run": (C.c_int, [_vp, _vp, _i64, _i32, _op, _vp, _vp, _vp, _vp]),
+    "lr_dense_adapt_result": (C.c_int, [_vp, _dp, _vp, C.POINTER(AdaptInfo)]),
+    "lr_dense_adapt_trace": (C.c_int, [_vp, _vp, _vp]),
+    "lr_dense_adapt_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
+_dense = None
+_factor = None
 _predict = None
 _acf = None
 _marg = None
@@ -274,11 +288,38 @@ def load_adapt():
     return bind_adapt(load())
 
 
+def bind_dense(L):
+    """`L` (a loaded library handle) with the dense-metric NUTS entry points bound; resolved once per handle."""
+    return _bind(L, DENSE_SYMBOLS, "_dense")
+
+
+def load_dense():
+    """The library with the dense-metric NUTS entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_dense(load())
+
+
 def load():
     """Load the HIP library (building it first if the sources are newer and hipcc is present)."""
     global _lib
-    if _lib is not None:
-        return _lib
+    if _lib is None:
+        _lib = _open()
+    return _lib
+
+
+def load_factor():
+    """liblogreg_hip.so itself with `lr_dense_factor` and `lr_last_error` bound.  The factorisation is host code with no device and no
+    model behind it, so it does not follow a handle that was put in load()'s place: the CPU test doubles hold SYMBOLS alone, and a
+    kernel object above one of their models still validates its matrix."""
+    global _factor
+    if _factor is None:
+        L = _open()
+        L.lr_dense_factor.restype, L.lr_dense_factor.argtypes = DENSE_SYMBOLS["lr_dense_factor"]
+        _factor = L
+    return _factor
+
+
+def _open():
+    """A checked handle of liblogreg_hip.so with SYMBOLS bound: current (rebuilt if stale), of these sources, of this binding's layout."""
     from . import build as _build
     if _build.built_extra() and _build.EXTRA_ENV not in os.environ:
         # a development build (e.g. -DLR_STAMPS: clock reads and printf in hot loops) left behind by a profiling tool must
@@ -300,14 +341,13 @@ def load():
         L = C.CDLL(LIB_PATH)
     except OSError as e:
         raise LogregHipError(f"cannot load {LIB_PATH}: {e}. There is no CPU fallback.") from e
-    _bind(L, SYMBOLS)  # (_lib remembers the handle only once the checks below have passed)
+    _bind(L, SYMBOLS)  # (load() remembers the handle only once the checks below have passed)
     have, want = L.lr_build_id().decode(), _build.source_hash()
     if have != want:
         raise LogregHipError(f"{LIB_PATH} was built from other sources (build id {have}, sources {want}); "
                              "run `python -m logreg_amd.build --force`")
     if L.lr_sizeof_run_opts() != C.sizeof(RunOpts):
         raise LogregHipError(f"lr_run_opts is {L.lr_sizeof_run_opts()} bytes in the library, {C.sizeof(RunOpts)} in the binding")
-    _lib = L
     return L
 
 

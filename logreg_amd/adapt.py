@@ -43,6 +43,14 @@ def _adapt_library(L=None):
         raise _lib.LogregHipError(f"this library has no warm-up entry points (include/logreg_hip_adapt.h): {e}") from e
 
 
+def _dense_library(L=None):
+    L = _lib.load() if L is None else L
+    try:
+        return _lib.bind_dense(_lib.bind_adapt(L))
+    except AttributeError as e:
+        raise _lib.LogregHipError(f"this library has no dense-metric entry points (include/logreg_hip_dense.h): {e}") from e
+
+
 def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
                 chain_offset=0, keep=False):
     """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
@@ -97,6 +105,69 @@ def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0
                                 "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
                                 "mean_accept_stat": counters["accept_stat_sum"] / W, "metric_skipped": int(info.metric_skipped),
                                 "windows": int(info.windows), "iterations": int(info.iterations), "seed": int(seed)})
+    if keep:
+        res.draws = draws
+    return res
+
+
+def nuts_warmup_dense(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, inv_metric=None, max_depth=10, adapt_metric=True, seed=None,
+                      chain_offset=0, keep=False):
+    """`nuts_warmup` for the DENSE metric (include/logreg_hip_dense.h "Warm-up"; Stan's metric=dense_e, NumPyro's dense_mass=True): the
+    windows pool one p x p covariance over chains and time and the sampler gets the full inverse metric.  It starts from `inv_metric`
+    (`[p, p]`, default the unit matrix); with `adapt_metric=False` only the step size is tuned to that fixed matrix -- what a metric
+    from elsewhere (`optimize.laplace_metric`, `covariance.dense_metric`) needs.
+
+    Returns what `nuts_warmup` returns with `inv_metric` `[p, p]` in place of `dmm` / `pre`, `metric_trace` `[windows, p, p]` (the
+    matrix after each window) and a dense `kernel` (`nutsKernel(lpost, glp, eps, max_depth=, inv_metric=res.inv_metric)`);
+    `info["metric_skipped"]` counts the windows whose matrix was not positive definite (the previous one stays)."""
+    from .kernels import _inv_metric_array
+    model = _model_of(lpost, "lpost")
+    if model is None or _model_of(glp, "glp") is not model:
+        raise ValueError("nuts_warmup_dense needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)")
+    W, max_depth = int(num_warmup), int(max_depth)
+    if W < 1:
+        raise ValueError(f"num_warmup must be >= 1, got {num_warmup}")
+    if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
+        raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
+    if not 0.0 < float(target_accept) < 1.0:
+        raise ValueError(f"target_accept must be in (0, 1), got {target_accept}")
+    if not (np.isfinite(eps) and float(eps) > 0):
+        raise ValueError(f"eps must be finite and > 0, got {eps}")
+    st = np.array(np.atleast_2d(np.asarray(init, dtype=np.float64)), dtype=model.np_dtype, order="C")
+    if st.ndim != 2 or st.shape[1] != model.p:
+        raise ValueError(f"init must be [p] or [C,p] with p={model.p}; got {np.shape(init)}")
+    p, Cn = model.p, st.shape[0]
+    sig0 = np.eye(p) if inv_metric is None else _inv_metric_array(inv_metric, p)
+    if not np.all(np.isfinite(np.tril(sig0))):
+        raise ValueError("inv_metric must be finite")
+    target_accept, eps, adapt_metric, chain_offset = float(target_accept), float(eps), bool(adapt_metric), int(chain_offset)
+    L = _dense_library(model._L)  # the library that made the model
+    _lib.require_gpu()
+    if seed is None:
+        seed = int(np.random.randint(0, 2**31 - 1))
+    seed = int(seed)
+    o = AdaptOpts(W=W, adapt_metric=int(adapt_metric), delta=target_accept, eps0=eps, dmm0=None)
+    h = C.c_void_p()
+    check(L.lr_dense_adapt_create(model.handle, Cn, C.byref(o), sig0.ctypes.data, C.byref(h)))
+    try:
+        counters = np.zeros(Cn, dtype=NUTS_COUNTERS)
+        draws = np.empty((W, Cn, p), dtype=model.np_dtype) if keep else None
+        opts = RunOpts(n_chains=Cn, chain_offset=chain_offset, thin=1, iters=1, seed=seed & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO, on_device=0)
+        check(L.lr_dense_adapt_run(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
+        e, info = C.c_double(), AdaptInfo()
+        sig = np.empty((p, p), dtype=np.float64)
+        check(L.lr_dense_adapt_result(h, C.byref(e), sig.ctypes.data, C.byref(info)))
+        trace = np.zeros((W, _lib.ADAPT_TRACE_COLS), dtype=np.float64)
+        metric_trace = np.zeros((info.n_windows, p, p), dtype=np.float64)
+        check(L.lr_dense_adapt_trace(h, trace.ctypes.data, metric_trace.ctypes.data if info.n_windows else None))
+    finally:
+        L.lr_dense_adapt_destroy(h)
+    res = SimpleNamespace(eps=float(e.value), inv_metric=sig, state=st.astype(np.float64), trace=trace, metric_trace=metric_trace,
+                          kernel=nutsKernel(lpost, glp, float(e.value), max_depth=max_depth, inv_metric=sig),
+                          info={"n_leapfrog": counters["n_leapfrog"].astype(np.int64), "divergent": counters["divergent"].astype(np.int64),
+                                "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
+                                "mean_accept_stat": counters["accept_stat_sum"] / W, "metric_skipped": int(info.metric_skipped),
+                                "windows": int(info.windows), "iterations": int(info.iterations), "seed": seed})
     if keep:
         res.draws = draws
     return res

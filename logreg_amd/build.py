@@ -78,7 +78,8 @@ def _sources():
                                                                         os.path.join(INCLUDE, "logreg_hip_marginals.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_loo.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_cov.h"),
-                                                                        os.path.join(INCLUDE, "logreg_hip_adapt.h")]
+                                                                        os.path.join(INCLUDE, "logreg_hip_adapt.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_dense.h")]
 
 
 def _dirs(alt: bool):

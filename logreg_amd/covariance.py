@@ -136,6 +136,18 @@ def metric(res) -> dict:
     return {"dmm": 1.0 / var, "pre": var}
 
 
+def dense_metric(res) -> np.ndarray:
+    """The dense inverse metric `[p, p]` of `nutsKernel(..., inv_metric=)` from a result: the covariance regularised as the warm-up
+    regularises a window's (include/logreg_hip_dense.h), n / (n + 5) cov + 1e-3 * 5 / (n + 5) I with n = nobs the draws behind it.
+    (`metric(res)` keeps its two diagonal keys.)  Every variance must be finite and positive."""
+    cov = np.asarray(res["cov"], dtype=np.float64)
+    var = np.diag(cov)
+    if not (np.all(np.isfinite(cov)) and np.all(var > 0)):
+        raise ValueError("dense_metric needs a finite covariance with a positive variance in every coordinate")
+    n = float(res["nobs"])
+    return (n / (n + 5.0)) * (0.5 * (cov + cov.T)) + 1e-3 * (5.0 / (n + 5.0)) * np.eye(cov.shape[0])
+
+
 def merge_covariance(results, center=None, scale=None) -> dict:
     """Results (or raw `(moment, chain_outer, sum, chain_sums, n)` tuples of `Covariance.tables()`, with `center=` and `scale=`) of
     disjoint sets of chains (shards, ranks) of one run with equal n, center and scale -> the result of the union: moment, chain_outer

@@ -19,6 +19,7 @@
 #include "../../include/logreg_hip_loo.h"
 #include "../../include/logreg_hip_cov.h"
 #include "../../include/logreg_hip_adapt.h"
+#include "../../include/logreg_hip_dense.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -38,7 +39,10 @@
 #include "lr_cov.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
+#include "lr_nuts_dense.h"
+#include "lr_dense.h"
 #include "lr_adapt.h"
+#include "lr_dense_adapt.h"
 #include "lr_hessian.h"
 #include "lr_mfma.h"
 #include "lr_predict.h"
@@ -196,6 +200,89 @@ int do_nuts_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o,
 int do_nuts(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
             void* out, lr_nuts_counters* counters, int8_t* depth_out) {
     LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_nuts_t, m, pl, st, o, eps, max_depth, dmm, state, out, counters, depth_out)
+    return bad_width(m);
+}
+
+// ---- NUTS under a dense metric (include/logreg_hip_dense.h; kernel: lr_nuts_dense.h, factorisation: lr_dense.h)
+struct DenseFactorHost {
+    std::vector<double> sigma;  // the lower triangle the factor was made from, row by row
+    std::vector<unsigned char> image;  // lr_nuts_dense.h `factor` in the model's dtype
+};
+template <typename T, int P> int dense_image_t(int p, const double* s, const double* R, const double* A, std::vector<unsigned char>* img) {
+    lr::dense_factor_image<T, P>(p, s, R, A, img);
+    return LR_OK;
+}
+// factorise inv_metric for model m (no device access); LR_ERR_INVALID with the reason
+int dense_factor_host(const lr_model* m, const char* who, const double* inv_metric, DenseFactorHost* f) {
+    if (!inv_metric) return fail(LR_ERR_INVALID, "%s: inv_metric is NULL", who);
+    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
+    const int p = m->p;
+    std::vector<double> s((size_t)p), R((size_t)p * p), A((size_t)p * p);
+    char why[200];
+    if (lr::dense_factor(p, inv_metric, s.data(), R.data(), A.data(), why, sizeof(why))) return fail(LR_ERR_INVALID, "%s: %s", who, why);
+    f->sigma.clear();
+    for (int i = 0; i < p; ++i) f->sigma.insert(f->sigma.end(), inv_metric + (size_t)i * p, inv_metric + (size_t)i * p + i + 1);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, dense_image_t, p, s.data(), R.data(), A.data(), &f->image)
+    return bad_width(m);
+}
+// the device image of `f` for launches on `st`: the model keeps the last one per stream (lr_model.h `dense`); another factor on the same
+// stream waits for the work enqueued there, which may still read the one it replaces
+int dense_factor_device(lr_model* m, hipStream_t st, const DenseFactorHost& f, void** out) {
+    lr_model::DenseFactor* slot = nullptr;
+    for (auto& e : m->dense)
+        if (e.stream == st) slot = &e;
+    if (!slot) {
+        if (m->dense.size() >= 16) {  // a caller cycling through streams (as the workspaces of lr_engine.h)
+            LR_HIP(hipDeviceSynchronize());
+            for (auto& e : m->dense)
+                if (e.p) (void)hipFree(e.p);
+            m->dense.clear();
+        }
+        void* p = nullptr;
+        if (hipMalloc(&p, f.image.size()) != hipSuccess) return fail(LR_ERR_NOMEM, "device allocation failed (the dense metric's factor: %zu bytes)", f.image.size());
+        m->dense.push_back({st, p, {}});
+        slot = &m->dense.back();
+    }
+    if (slot->sigma != f.sigma) {
+        LR_HIP(hipStreamSynchronize(st));
+        slot->sigma.clear();  // (a failed copy leaves no claim on what the buffer holds)
+        LR_HIP(hipMemcpy(slot->p, f.image.data(), f.image.size(), hipMemcpyHostToDevice));
+        slot->sigma = f.sigma;
+    }
+    *out = slot->p;
+    return LR_OK;
+}
+
+template <typename T, int P>
+int do_nuts_dense_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const void* factor, void* state,
+                    void* out, lr_nuts_counters* counters, int8_t* depth_out) {
+    auto ma = model_args<T, P>(m);
+    lr::NutsDenseArgs<T, P> na{};
+    na.state = static_cast<T*>(state);
+    na.out = static_cast<T*>(out);
+    na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
+    na.depth_out = depth_out;
+    na.C = o->n_chains;
+    na.chain_offset = o->chain_offset;
+    na.iters = o->iters;
+    na.thin = o->thin;
+    na.iter_offset = o->iter_offset;
+    na.seed = o->seed;
+    na.p = m->p;
+    na.max_depth = max_depth;
+    na.step = (T)eps;
+    na.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    na.factor = static_cast<const T*>(factor);
+    lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const int rc = m->table->launch_nuts_dense(&cfg, o->n_chains, &ma, &na);
+    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "dense NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return LR_OK;
+}
+int do_nuts_dense(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const DenseFactorHost& f, void* state,
+                  void* out, lr_nuts_counters* counters, int8_t* depth_out) {
+    void* factor = nullptr;
+    if (const int rc = dense_factor_device(m, st, f, &factor)) return rc;
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_nuts_dense_t, m, pl, st, o, eps, max_depth, factor, state, out, counters, depth_out)
     return bad_width(m);
 }
 
@@ -386,6 +473,8 @@ void lr_model_destroy(lr_model* m) {
     if (m->d_rows_tw) (void)hipFree(m->d_rows_tw);
     for (auto& e : m->ws)
         if (e.p) (void)hipFree(e.p);
+    for (auto& e : m->dense)
+        if (e.p) (void)hipFree(e.p);
     if (m->d_xblk) (void)hipFree(m->d_xblk);
     if (m->d_xblk1) (void)hipFree(m->d_xblk1);
     if (m->d_xblk1h) (void)hipFree(m->d_xblk1h);
@@ -551,6 +640,27 @@ int lr_run_nuts(lr_model* m, void* state, double eps, int32_t max_depth, const d
     return run_request(m, LR_KIND_NUTS, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
                        [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
                            return do_nuts(m, pl, st, oo, eps, max_depth, dmm, d.state, d.out, static_cast<lr_nuts_counters*>(d.tally), d.depth_out);
+                       });
+}
+
+// NUTS under a dense metric (include/logreg_hip_dense.h): lr_run_nuts with the factor of inv_metric in place of dmm
+int lr_dense_factor(int32_t p, const double* inv_metric, double* s, double* R, double* A) {
+    if (!inv_metric) return fail(LR_ERR_INVALID, "lr_dense_factor: inv_metric is NULL");
+    char why[200];
+    if (lr::dense_factor(p, inv_metric, s, R, A, why, sizeof(why))) return fail(LR_ERR_INVALID, "lr_dense_factor: %s", why);
+    return LR_OK;
+}
+
+int lr_run_nuts_dense(lr_model* m, void* state, double eps, int32_t max_depth, const double* inv_metric, const lr_run_opts* o, void* out,
+                      lr_nuts_counters* counters, int8_t* depth_out) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
+    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
+    DenseFactorHost f;
+    if (const int rc = dense_factor_host(m, "lr_run_nuts_dense", inv_metric, &f)) return rc;
+    return run_request(m, kKindNutsDense, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
+                           return do_nuts_dense(m, pl, st, oo, eps, max_depth, f, d.state, d.out, static_cast<lr_nuts_counters*>(d.tally), d.depth_out);
                        });
 }
 
@@ -1233,6 +1343,14 @@ struct lr_adapt {
     double* d_fixed = nullptr;
     size_t words = 0, tune_bytes = 0;
     Workspace st_state, st_out, st_tally, st_depth, st_astat;  // a call made with host pointers stages its arrays here
+    // lr_dense_adapt_create (include/logreg_hip_dense.h): the iterations run k_nuts_dense under d_factor (lr_nuts_dense.h `factor`)
+    void* d_factor = nullptr;
+    bool dense_metric = false;     // adapt_metric: the windows re-estimate Sigma (dense_window_end)
+    double* d_comoment = nullptr;  // the window's triple | the workgroups' triples [B] (lr_dense_adapt.h)
+    std::vector<double> sigma;     // the current inverse metric [p][p]
+    std::vector<double> sigma_trace;  // [n_windows][p][p]: Sigma after each window done
+    int64_t dense_skipped = 0;     // windows whose Sigma was refused (the previous metric stays)
+    int dense_windows = 0;
     int p() const { return m->p; }
     size_t o_dmm() const { return 8; }
     size_t o_win() const { return o_dmm() + (size_t)p(); }
@@ -1286,6 +1404,36 @@ int adapt_tune_image(int p, double eps, const double* dmm, std::vector<unsigned 
     return LR_OK;
 }
 
+// The end of a dense metric's window (include/logreg_hip_dense.h "Warm-up"): the one host synchronisation of the warm-up.  Reads the
+// window's pooled triple, forms S = M / (n - 1) and Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I, factorises it and replaces the device
+// factor; a Sigma that lr_dense_factor refuses keeps the previous metric and is counted.  The triple is emptied for the next window.
+int dense_window_end(lr_adapt* h, hipStream_t st, int P) {
+    const int p = h->p();
+    const size_t tw = (size_t)lr::dense_triple_words(P);
+    std::vector<double> win(tw);
+    LR_HIP(hipStreamSynchronize(st));
+    LR_HIP(hipMemcpy(win.data(), h->d_comoment, tw * sizeof(double), hipMemcpyDeviceToHost));
+    const double n = win[0];
+    std::vector<double> sig((size_t)p * p);
+    for (int j = 0; j < p; ++j)
+        for (int l = 0; l <= j; ++l) {
+            const double S = win[1 + P + (size_t)j * P + l] / (n - 1.0);
+            const double v = (n / (n + 5.0)) * S + (j == l ? 1e-3 * (5.0 / (n + 5.0)) : 0.0);
+            sig[(size_t)j * p + l] = sig[(size_t)l * p + j] = v;
+        }
+    DenseFactorHost f;
+    if (dense_factor_host(h->m, "lr_dense_adapt_run", sig.data(), &f) == LR_OK) {
+        LR_HIP(hipMemcpy(h->d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice));
+        h->sigma = sig;
+    } else {
+        ++h->dense_skipped;
+    }
+    std::copy(h->sigma.begin(), h->sigma.end(), h->sigma_trace.begin() + (size_t)h->dense_windows * p * p);
+    ++h->dense_windows;
+    LR_HIP(hipMemsetAsync(h->d_comoment, 0, tw * sizeof(double), st));
+    return LR_OK;
+}
+
 // `iters` iterations, three launches each, on `st`; every pointer is device memory
 template <typename T, int P>
 int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
@@ -1314,19 +1462,38 @@ int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts
         na.stats = lr::StatsArgs{nullptr, 1, 0};
         na.tune = tune;
         na.astat = astat_out ? astat_out + (size_t)i * h->C : h->astat();
-        const int rc = m->table->launch_nuts_tuned(&cfg, h->C, &ma, &na);
+        int rc;
+        if (h->d_factor) {  // the same iteration under the handle's dense metric: `step` alone comes from the tuning block
+            lr::NutsDenseTunedArgs<T, P> nd{};
+            static_cast<lr::NutsArgs<T, P>&>(nd) = na;
+            nd.factor = static_cast<const T*>(h->d_factor);
+            nd.tune = na.tune;
+            nd.astat = na.astat;
+            rc = m->table->launch_nuts_dense_tuned(&cfg, h->C, &ma, &nd);
+        } else {
+            rc = m->table->launch_nuts_tuned(&cfg, h->C, &ma, &na);
+        }
         if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "lr_adapt_run: NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
         const bool in_window = h->window < h->n_windows && h->t >= (h->window ? h->ends[h->window - 1] : h->init);
         const bool window_end = in_window && h->t == h->ends[h->window] - 1;
         hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), na.astat, h->C, m->p, in_window ? 1 : 0,
                            dev.partial);
         LR_HIP(hipGetLastError());
+        if (h->dense_metric && in_window) {  // the pooled co-moment of the dense metric's window (lr_dense_adapt.h)
+            double* part = h->d_comoment + lr::dense_triple_words(P);
+            hipLaunchKernelGGL((lr::k_dense_comoment_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), h->C, m->p, part);
+            LR_HIP(hipGetLastError());
+            hipLaunchKernelGGL((lr::k_dense_comoment_merge<P>), dim3(1), dim3(P * P < 64 ? 64 : P * P), 0, st, part, h->B, m->p, h->d_comoment);
+            LR_HIP(hipGetLastError());
+        }
         const lr::AdaptStep s{h->C, h->t, m->p, h->m_since + 1, in_window ? h->window : -1, window_end ? 1 : 0, h->t == h->W - 1 ? 1 : 0, h->delta, h->gamma, h->t0, h->kappa};
         hipLaunchKernelGGL((lr::k_adapt_update<T, P>), dim3(1), dim3(64), 0, st, dev, s, tune);
         LR_HIP(hipGetLastError());
         ++h->t;
         h->m_since = window_end ? 0 : h->m_since + 1;
         if (window_end) ++h->window;
+        if (h->dense_metric && window_end)
+            if (const int rcw = dense_window_end(h, st, P)) return rcw;
     }
     return LR_OK;
 }
@@ -1426,7 +1593,7 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
     if (const int rc = check_opts(m, &oo, true)) return rc;
     LR_HIP(hipSetDevice(m->device));
     Plan pl;
-    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl)) return rc;
+    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl, h->d_factor != nullptr)) return rc;
     if (iters == 0) return LR_OK;
     if (oo.on_device) return adapt_enqueue_checked(h, pl, (hipStream_t)oo.stream, &oo, max_depth, state, out, counters, depth_out, astat_out, iters);
     const size_t C = (size_t)h->C, sbytes = C * m->p * m->esize();
@@ -1475,9 +1642,77 @@ int lr_adapt_trace(lr_adapt* h, double* trace, double* metric) {
 void lr_adapt_destroy(lr_adapt* h) {
     if (!h) return;
     (void)hipSetDevice(h->m->device);
-    free_all({h->d_fixed, h->st_state.p, h->st_out.p, h->st_tally.p, h->st_depth.p, h->st_astat.p});
+    free_all({h->d_fixed, h->st_state.p, h->st_out.p, h->st_tally.p, h->st_depth.p, h->st_astat.p, h->d_factor, h->d_comoment});
     delete h;
 }
+
+// the warm-up under a dense metric (include/logreg_hip_dense.h): an lr_adapt whose iterations run k_nuts_dense and whose windows, with
+// adapt_metric, re-estimate the full inverse metric
+int lr_dense_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, const double* inv_metric, lr_adapt** out) {
+    if (!m || !o || !out) return fail(LR_ERR_INVALID, "lr_dense_adapt_create: model / opts / out is NULL");
+    if (o->dmm0) return fail(LR_ERR_INVALID, "lr_dense_adapt_create: dmm0 must be NULL (the metric is inv_metric)");
+    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
+    const int p = m->p;
+    std::vector<double> sigma((size_t)p * p, 0.0);
+    if (inv_metric) {
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j <= i; ++j) sigma[(size_t)i * p + j] = sigma[(size_t)j * p + i] = inv_metric[(size_t)i * p + j];
+    } else {
+        for (int i = 0; i < p; ++i) sigma[(size_t)i * p + i] = 1.0;  // NULL: the unit metric
+    }
+    DenseFactorHost f;
+    if (const int rc = dense_factor_host(m, "lr_dense_adapt_create", sigma.data(), &f)) return rc;
+    if (!m->table || !m->table->launch_nuts_dense_tuned) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
+    lr_adapt* h = nullptr;
+    if (const int rc = lr_adapt_create(m, C, o, &h)) return rc;
+    h->dense_metric = h->n_windows > 0;
+    h->sigma = sigma;
+    h->sigma_trace.assign((size_t)h->n_windows * p * p, 0.0);
+    const size_t cm_bytes = (size_t)(h->B + 1) * lr::dense_triple_words(m->P) * sizeof(double);
+    hipError_t e = hipMalloc(&h->d_factor, f.image.size());
+    if (e != hipSuccess) h->d_factor = nullptr;
+    if (e == hipSuccess && h->dense_metric) {
+        e = hipMalloc((void**)&h->d_comoment, cm_bytes);
+        if (e != hipSuccess) h->d_comoment = nullptr;
+    }
+    if (e != hipSuccess) {
+        lr_adapt_destroy(h);
+        return fail(LR_ERR_NOMEM, "lr_dense_adapt_create: allocating the metric's factor and co-moments failed");
+    }
+    e = hipMemcpy(h->d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h->d_comoment) {  // an empty window
+        const std::vector<double> zero((size_t)lr::dense_triple_words(m->P), 0.0);
+        e = hipMemcpy(h->d_comoment, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        lr_adapt_destroy(h);
+        return fail(LR_ERR_HIP, "lr_dense_adapt_create: copying the metric's factor failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return LR_OK;
+}
+int lr_dense_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters,
+                       int8_t* depth_out, double* astat_out) {
+    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_run: the handle is not one of lr_dense_adapt_create");
+    return lr_adapt_run(h, state, iters, max_depth, o, out, counters, depth_out, astat_out);
+}
+int lr_dense_adapt_result(lr_adapt* h, double* eps, double* inv_metric, lr_adapt_info* info) {
+    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_result: the handle is not one of lr_dense_adapt_create");
+    if (const int rc = lr_adapt_result(h, eps, nullptr, info)) return rc;
+    if (inv_metric) std::copy(h->sigma.begin(), h->sigma.end(), inv_metric);
+    if (info) {
+        info->metric_skipped = h->dense_skipped;
+        info->windows = h->dense_windows;
+    }
+    return LR_OK;
+}
+int lr_dense_adapt_trace(lr_adapt* h, double* trace, double* metric) {
+    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_trace: the handle is not one of lr_dense_adapt_create");
+    if (const int rc = lr_adapt_trace(h, trace, nullptr)) return rc;
+    if (metric) std::copy(h->sigma_trace.begin(), h->sigma_trace.end(), metric);
+    return LR_OK;
+}
+void lr_dense_adapt_destroy(lr_adapt* h) { lr_adapt_destroy(h); }
 
 // ---- PSIS-LOO: the pointwise log-likelihood matrix and its Pareto-smoothed leave-one-out summary (include/logreg_hip_loo.h; kernels: lr_loo.h)
 }  // extern "C"

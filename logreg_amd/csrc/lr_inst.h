@@ -75,6 +75,10 @@ struct InstTable {
     int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
     // ... and its TUNED instantiation, step and metric from a device block (the warm-up, lr_adapt.h); `nuts_args` is a NutsTunedArgs<T,P>
     int (*launch_nuts_tuned)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
+    // NUTS under a dense metric (lr_nuts_dense.h); `nuts_args` is a NutsDenseArgs<T,P> / NutsDenseTunedArgs<T,P>; cfg->lds_bytes = rows +
+    // checkpoints + the two matrices
+    int (*launch_nuts_dense)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
+    int (*launch_nuts_dense_tuned)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
 };
 
 }  // namespace lr

@@ -3,6 +3,7 @@
 #include "lr_inst.h"
 #include "lr_kernels.h"
 #include "lr_nuts.h"
+#include "lr_nuts_dense.h"
 #include "lr_tall.h"
 #if LR_DTYPE == 0 && LR_P >= 8
 #include "lr_mfma.h"
@@ -298,8 +299,24 @@ int launch_nuts_tuned(const LaunchCfg* cfg, int64_t C, const void* model_args, c
     return launch_capped<&k_nuts<T, P, MODE_LDS, 0, true>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
 }
 
+// ... and under a dense metric (lr_nuts_dense.h)
+int launch_nuts_dense(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
+    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
+    const auto& a = *static_cast<const NutsDenseArgs<T, P>*>(nuts_args);
+    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
+    return launch_capped<&k_nuts_dense<T, P, MODE_LDS, 0>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
+}
+
+int launch_nuts_dense_tuned(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
+    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
+    const auto& a = *static_cast<const NutsDenseTunedArgs<T, P>*>(nuts_args);
+    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
+    return launch_capped<&k_nuts_dense<T, P, MODE_LDS, 0, true>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
+}
+
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_nuts_tuned};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_nuts_tuned,
+                          &launch_nuts_dense, &launch_nuts_dense_tuned};
 
 }  // namespace
 }  // namespace lr

@@ -162,6 +162,10 @@ struct lr_model {
     std::vector<Side> sides;
     struct Ws { hipStream_t stream; void* p; size_t bytes; };
     std::vector<Ws> ws;
+    // dense NUTS (include/logreg_hip_dense.h): the device image of the factor of the last inv_metric a stream ran with (lr_nuts_dense.h
+    // `factor`), one per caller stream as the workspaces; `sigma` is the lower triangle it was made from
+    struct DenseFactor { hipStream_t stream; void* p; std::vector<double> sigma; };
+    std::vector<DenseFactor> dense;
     size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
 };
 

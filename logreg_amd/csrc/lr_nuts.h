@@ -77,8 +77,66 @@ __device__ __forceinline__ double nuts_lae(double a, double b) {  // log(exp(a) 
     return mx + log1p(exp(d));
 }
 
-template <typename T, int P, int MODE, int R, bool TUNED = false>
-__global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P, TUNED> a) {
+// The metric as a policy of the tree loop (nuts_run): what the loop asks of it is the momentum of a draw, the position update of a
+// leapfrog step, the kinetic energy and the generalised U-turn criterion.  NutsDiagMetric is the diagonal metric of
+// include/logreg_hip_nuts.h; NutsDenseMetric (lr_nuts_dense.h) the full matrix of include/logreg_hip_dense.h.  Every sum over the
+// coordinates is group_sum<16> in both.
+template <typename T, int P, bool TUNED> struct NutsDiagMetric {
+    static constexpr int NK = (P + 15) / 16;
+    using Args = NutsArgsOf<T, P, TUNED>;
+    T ca[NK], cb[NK], cc[NK];
+    // (lds: the workgroup's LDS behind the checkpoints -- the diagonal metric keeps nothing there)
+    __device__ __forceinline__ void load(const Args& a, int r, T* lds) {
+        (void)lds;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int j = r + 16 * k, js = j < P ? j : 0;
+            if constexpr (TUNED) {
+                ca[k] = j < P ? a.tune->a[js] : T(0);
+                cb[k] = j < P ? a.tune->b[js] : T(0);
+                cc[k] = j < P ? a.tune->c[js] : T(0);
+            } else {
+                ca[k] = j < P ? a.a[js] : T(0);
+                cb[k] = j < P ? a.b[js] : T(0);
+                cc[k] = j < P ? a.c[js] : T(0);
+            }
+        }
+    }
+    // p = sqrt(dmm) z
+    __device__ __forceinline__ void momentum(const T (&z)[NK], T (&pm)[NK]) const {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) pm[k] = z[k] * ca[k];
+    }
+    // q += +-eps p / dmm (eps is folded into cb)
+    __device__ __forceinline__ void drift(bool fwd, T step, const T (&pm)[NK], T (&q)[NK]) const {
+        (void)step;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) q[k] = fma_t(fwd ? cb[k] : -cb[k], pm[k], q[k]);
+    }
+    // generalised U-turn criterion: rho' = rho - (pa + pb) / 2; (pa / dmm) . rho' <= 0 or (pb / dmm) . rho' <= 0
+    __device__ __forceinline__ bool turning(const T (&pa)[NK], const T (&pb)[NK], const T (&rh)[NK]) const {
+        T sa = T(0), sb = T(0);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const T rr = fma_t(T(-0.5), pa[k] + pb[k], rh[k]);
+            sa = fma_t(cc[k] * pa[k], rr, sa);
+            sb = fma_t(cc[k] * pb[k], rr, sb);
+        }
+        sa = group_sum<16>(sa);
+        sb = group_sum<16>(sb);
+        return sa <= T(0) || sb <= T(0);
+    }
+    __device__ __forceinline__ double kinetic2(const T (&pm)[NK]) const {  // sum p^2 / dmm
+        T s = T(0);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) s = fma_t(pm[k] * pm[k], cc[k], s);
+        return (double)group_sum<16>(s);
+    }
+};
+
+// the whole kernel but its name: k_nuts and k_nuts_dense (lr_nuts_dense.h) are this body under their metric
+template <typename T, int P, int MODE, int R, bool TUNED, typename Metric>
+__device__ __forceinline__ void nuts_run(const ModelArgs<T, P>& m, const typename Metric::Args& a) {
     static_assert(MODE == MODE_LDS, "rows in LDS");
     constexpr int G = 16, NK = (P + 15) / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -91,20 +149,13 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P
     const uint64_t gchain = (uint64_t)(a.chain_offset + chain);
     const int gbase = (int)(threadIdx.x & 63) - gl;  // first lane of the chain's row in the wave
 
-    T x[NK], ca[NK], cb[NK], cc[NK], civ[NK];
+    T x[NK], civ[NK];
+    Metric metric;
+    metric.load(a, r, reinterpret_cast<T*>(smem_raw) + m.n * (P + kLdsRowPad<T>) + (size_t)2 * a.max_depth * NK * 256);
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const int j = r + 16 * k, js = j < P ? j : 0;
         x[k] = j < a.p ? a.state[chain * a.p + j] : T(0);
-        if constexpr (TUNED) {
-            ca[k] = j < P ? a.tune->a[js] : T(0);
-            cb[k] = j < P ? a.tune->b[js] : T(0);
-            cc[k] = j < P ? a.tune->c[js] : T(0);
-        } else {
-            ca[k] = j < P ? a.a[js] : T(0);
-            cb[k] = j < P ? a.b[js] : T(0);
-            cc[k] = j < P ? a.c[js] : T(0);
-        }
         civ[k] = j < P ? m.prior.inv_var[js] : T(0);
     }
     const double lprior_const = m.prior.lprior_const;
@@ -142,25 +193,8 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P
         }
         return ll + (lprior_const - 0.5 * (double)row_sum(qd));
     };
-    // generalised U-turn criterion: rho' = rho - (pa + pb) / 2; (pa / dmm) . rho' <= 0 or (pb / dmm) . rho' <= 0
-    auto turning = [&](const T (&pa)[NK], const T (&pb)[NK], const T (&rh)[NK]) -> bool {
-        T sa = T(0), sb = T(0);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const T rr = fma_t(T(-0.5), pa[k] + pb[k], rh[k]);
-            sa = fma_t(cc[k] * pa[k], rr, sa);
-            sb = fma_t(cc[k] * pb[k], rr, sb);
-        }
-        sa = row_sum(sa);
-        sb = row_sum(sb);
-        return sa <= T(0) || sb <= T(0);
-    };
-    auto kinetic2 = [&](const T (&pm)[NK]) -> double {  // sum p^2 / dmm
-        T s = T(0);
-#pragma unroll
-        for (int k = 0; k < NK; ++k) s = fma_t(pm[k] * pm[k], cc[k], s);
-        return (double)row_sum(s);
-    };
+    auto turning = [&](const T (&pa)[NK], const T (&pb)[NK], const T (&rh)[NK]) -> bool { return metric.turning(pa, pb, rh); };
+    auto kinetic2 = [&](const T (&pm)[NK]) -> double { return metric.kinetic2(pm); };
 
     T g[NK];
     double lp = evaluate(x, g);
@@ -190,12 +224,13 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P
                                         (uint32_t)(a.seed >> 32));
 
             T Lq[NK], Lp[NK], Lg[NK], Rq[NK], Rp[NK], Rg[NK], cq[NK], cp[NK], cg[NK];
-            T rho[NK], rhos[NK], pfirst[NK], pinner[NK], px[NK], pg[NK], sx[NK], sg[NK];
+            T rho[NK], rhos[NK], pfirst[NK], pinner[NK], px[NK], pg[NK], sx[NK], sg[NK], p0[NK];
+            metric.momentum(z, p0);
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 Lq[k] = Rq[k] = px[k] = sx[k] = x[k];
                 Lg[k] = Rg[k] = pg[k] = sg[k] = g[k];
-                Lp[k] = Rp[k] = rho[k] = z[k] * ca[k];
+                Lp[k] = Rp[k] = rho[k] = p0[k];
                 rhos[k] = pfirst[k] = T(0);
             }
             double plp = lp, slp = lp;
@@ -225,10 +260,8 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P
                 // leapfrog from the moving end, step +-eps
                 const T hs = fwd ? heps : -heps;
 #pragma unroll
-                for (int k = 0; k < NK; ++k) {
-                    cp[k] = fma_t(hs, cg[k], cp[k]);
-                    cq[k] = fma_t(fwd ? cb[k] : -cb[k], cp[k], cq[k]);
-                }
+                for (int k = 0; k < NK; ++k) cp[k] = fma_t(hs, cg[k], cp[k]);
+                metric.drift(fwd, step, cp, cq);
                 const double lpl = evaluate(cq, cg);
 #pragma unroll
                 for (int k = 0; k < NK; ++k) cp[k] = fma_t(hs, cg[k], cp[k]);
@@ -384,6 +417,11 @@ __global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P
         if constexpr (TUNED)
             if (r == 0) a.astat[chain] = last_stat;
     }
+}
+
+template <typename T, int P, int MODE, int R, bool TUNED = false>
+__global__ void __launch_bounds__(256) k_nuts(ModelArgs<T, P> m, NutsArgsOf<T, P, TUNED> a) {
+    nuts_run<T, P, MODE, R, TUNED, NutsDiagMetric<T, P, TUNED>>(m, a);
 }
 
 }  // namespace lr

@@ -524,24 +524,32 @@ int make_plan(const PlanReq& q, Plan* out) {
 size_t nuts_lds_bytes(const lr_model* m, int max_depth) {
     return lds_rows_bytes(m) + (size_t)2 * max_depth * ((m->P + 15) / 16) * 256 * m->esize();
 }
-int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out) {
+// ... and under a dense metric (include/logreg_hip_dense.h) the two P x P matrices of lr_nuts_dense.h behind them
+constexpr int kKindNutsDense = LR_KIND_NUTS + 1;  // plan_run only: not a kind of the ABI
+size_t nuts_dense_lds_bytes(const lr_model* m) { return (size_t)2 * m->P * m->P * m->esize(); }
+int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, bool dense = false) {
     if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
     if (mode == LR_MODE_STEPWISE) return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine has no NUTS kernel; NUTS runs with the rows in LDS");
     if (mode != LR_MODE_AUTO && mode != LR_MODE_LDS)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: mode %d has no NUTS kernel (rows in LDS only: LR_MODE_LDS or LR_MODE_AUTO)", mode);
     if (group != 0 && group != 16) return fail(LR_ERR_UNSUPPORTED, "NUTS: group %d has no NUTS kernel (16 lanes per chain only)", group);
-    const size_t bytes = nuts_lds_bytes(m, max_depth);
+    const size_t bytes = nuts_lds_bytes(m, max_depth) + (dense ? nuts_dense_lds_bytes(m) : 0);
+    if (bytes > kLdsBudget && dense)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes), the U-turn checkpoints and the dense metric's two matrices (%zu bytes) need %zu bytes "
+                    "of LDS, beyond the %zu a workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n,
+                    lds_rows_bytes(m), nuts_dense_lds_bytes(m), bytes, kLdsBudget);
     if (bytes > kLdsBudget)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes) and the U-turn checkpoints need %zu bytes of LDS, beyond the %zu a "
                     "workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n, lds_rows_bytes(m), bytes, kLdsBudget);
-    if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
+    if (!m->table || !m->table->launch_nuts || (dense && !m->table->launch_nuts_dense)) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
     *out = Plan{lr::MODE_LDS, 16, 0, bytes};
     return LR_OK;
 }
 
-// the plan of a run of `kind` (LR_KIND_*): every lr_run_*, lr_plan_run_info and tests/host/plan_harness.hip come through here
+// the plan of a run of `kind` (LR_KIND_*, or kKindNutsDense): every lr_run_*, lr_plan_run_info and tests/host/plan_harness.hip come through here
 int plan_run(const lr_model* m, int kind, const lr_run_opts* o, int max_depth, Plan* out) {
-    return kind == LR_KIND_NUTS ? plan_nuts(m, o->group, o->mode, max_depth, out) : make_plan(plan_request(m, kind, o), out);
+    if (kind == LR_KIND_NUTS || kind == kKindNutsDense) return plan_nuts(m, o->group, o->mode, max_depth, out, kind == kKindNutsDense);
+    return make_plan(plan_request(m, kind, o), out);
 }
 
 // `group` means different things per mode (include/logreg_hip.h): lanes per chain (REG / LDS / GLOBAL / AUTO on narrow models:

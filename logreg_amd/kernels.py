@@ -151,7 +151,11 @@ class FusedKernel:
         (lr_nuts_counters) and the optional tree depths of the kept rows instead."""
         L = self.model._L
         h = self.model.handle
-        if self.kind == "nuts":
+        if self.kind == "nuts" and self.params.get("inv_metric") is not None:  # dense metric (include/logreg_hip_dense.h)
+            v = self.params["inv_metric"]
+            check(_lib.bind_dense(L).lr_run_nuts_dense(h, state_ptr, float(self.params["eps"]), int(self.params["max_depth"]), v.ctypes.data,
+                                                       C.byref(opts), out_ptr, counters_ptr, depth_ptr))
+        elif self.kind == "nuts":
             v = self._vec("dmm")
             check(_lib.bind_nuts(L).lr_run_nuts(h, state_ptr, float(self.params["eps"]), int(self.params["max_depth"]), v.ctypes.data,
                                                 C.byref(opts), out_ptr, counters_ptr, depth_ptr))
@@ -286,10 +290,35 @@ def hmcKernel(lpi, glpi, eps=1e-4, l=10, dmm=1):
     return kern
 
 
-def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10):
+def dense_factor(inv_metric):
+    """-> (s [p], R [p, p], A [p, p]) of a dense inverse metric Sigma (include/logreg_hip_dense.h "Factorisation", `lr_dense_factor`: host
+    code, no device): s = sqrt(diag Sigma), R = Sigma / (s s^T), A = L^-T with R = L L^T.  p = (A z) / s has covariance Sigma^-1.
+    Only the lower triangle is read; a Sigma that is not finite or not positive definite raises."""
+    sig = _inv_metric_array(inv_metric, None)
+    p = sig.shape[0]
+    s, R, A = np.empty(p), np.empty((p, p)), np.empty((p, p))
+    L = _lib.load_factor()  # the library itself, whichever handle load() returns: the error text below is then its own too
+    rc = L.lr_dense_factor(p, sig.ctypes.data, s.ctypes.data, R.ctypes.data, A.ctypes.data)
+    if rc != 0:
+        raise _lib.LogregHipError(f"liblogreg_hip error {rc}: {L.lr_last_error().decode()}")
+    return s, R, A
+
+
+def _inv_metric_array(inv_metric, p):
+    sig = np.array(inv_metric, dtype=np.float64, order="C")
+    if sig.ndim != 2 or sig.shape[0] != sig.shape[1] or (p is not None and sig.shape[0] != p):
+        raise ValueError(f"inv_metric must be a square matrix [p, p]" + (f" with p={p}" if p is not None else "") + f"; got {np.shape(inv_metric)}")
+    return sig
+
+
+def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10, *, inv_metric=None):
     """The No-U-Turn sampler with diagonal metric, in the reference HMC's convention (fit-np-hmc.py:65-87): p ~ N(0, dmm),
     H = -lpi(q) + sum(p^2 / dmm) / 2, q += eps * p / dmm.  Multinomial NUTS, iterative with U-turn checkpoints, at most `max_depth`
     doublings (DESIGN.md "NUTS").  `blackjax.nuts(lpost, eps, pre)` (fit-blackjax-nuts.py:101) is `nutsKernel(lpost, glp, eps, 1 / pre)`.
+
+    `inv_metric=` a `[p, p]` symmetric positive definite matrix selects the DENSE metric instead (`dmm` is then not read): BlackJAX's
+    matrix `inverse_mass_matrix`, about the posterior covariance -- p ~ N(0, inv_metric^-1), H = -lpi(q) + p^T inv_metric p / 2,
+    q += eps * inv_metric p (include/logreg_hip_dense.h).  `dmm` is the diagonal case inv_metric = diag(1 / dmm).
 
     A LogReg's closures give a FusedKernel (include/logreg_hip_nuts.h); any other callables a plain NumPy NUTS that draws from
     NumPy's global generator, like the other generic kernels."""
@@ -297,16 +326,36 @@ def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10):
     if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
         raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
     model = _model_of(lpi, "lpost")
-    if model is not None and _model_of(glpi, "glp") is model:
+    fused = model is not None and _model_of(glpi, "glp") is model
+    if inv_metric is not None:
+        sig = _inv_metric_array(inv_metric, model.p if fused else None)
+        factor = dense_factor(sig)  # refuses what is not finite or not positive definite, here rather than at the first launch
+        if fused:
+            return FusedKernel("nuts", model, eps=float(eps), inv_metric=sig, max_depth=max_depth)
+        return _numpy_nuts(lpi, glpi, float(eps), None, max_depth, dense=(sig, factor))
+    if fused:
         return FusedKernel("nuts", model, eps=float(eps), dmm=dmm, max_depth=max_depth)
     return _numpy_nuts(lpi, glpi, float(eps), dmm, max_depth)
 
 
-def _numpy_nuts(lpi, glpi, eps, dmm, max_depth):
+def _numpy_nuts(lpi, glpi, eps, dmm, max_depth, dense=None):
     """The same algorithm on NumPy arrays for arbitrary callables (the generic path: NumPy's global generator, no model arithmetic of
-    its own)."""
+    its own).  `dense` = (Sigma, (s, R, A)): the dense metric -- `c` below is then the matrix Sigma, applied as a product."""
+    if dense is not None:
+        sigma, (s_, _, A_) = dense
+        sigma = np.tril(sigma) + np.tril(sigma, -1).T  # the lower triangle, as the library reads it
+
+    def velocity(c, v):  # (inverse metric) v
+        return c @ v if dense is not None else c * v
+
+    def kinetic2(c, v):
+        return np.dot(v, c @ v) if dense is not None else np.sum(c * v * v)
+
     def turning(c, a, b, rho):
         r = rho - 0.5 * (a + b)
+        if dense is not None:
+            r = c @ r
+            return np.dot(a, r) <= 0 or np.dot(b, r) <= 0
         return np.dot(c * a, r) <= 0 or np.dot(c * b, r) <= 0
 
     def lae(a, b):
@@ -314,11 +363,15 @@ def _numpy_nuts(lpi, glpi, eps, dmm, max_depth):
 
     def kern(q):
         q = np.asarray(q, dtype=np.float64)
-        dm = np.broadcast_to(np.asarray(dmm, dtype=np.float64), q.shape)
-        c = 1.0 / dm
         x, g, lp = q, np.asarray(glpi(q), dtype=np.float64), float(lpi(q))
-        p0 = np.random.randn(len(q)) * np.sqrt(dm)
-        H0 = 0.5 * np.sum(c * p0 * p0) - lp
+        if dense is not None:
+            c = sigma
+            p0 = (A_ @ np.random.randn(len(q))) / s_
+        else:
+            dm = np.broadcast_to(np.asarray(dmm, dtype=np.float64), q.shape)
+            c = 1.0 / dm
+            p0 = np.random.randn(len(q)) * np.sqrt(dm)
+        H0 = 0.5 * kinetic2(c, p0) - lp
         ends = {-1: (x, p0, g), 1: (x, p0, g)}
         rho, W, prop = p0.copy(), 0.0, x
         for d in range(max_depth):
@@ -328,10 +381,10 @@ def _numpy_nuts(lpi, glpi, eps, dmm, max_depth):
             sub = pfirst = None
             for i in range(2 ** d):
                 cp = cp + sgn * 0.5 * eps * cg
-                cq = cq + sgn * eps * c * cp
+                cq = cq + sgn * eps * velocity(c, cp)
                 lpl, cg = float(lpi(cq)), np.asarray(glpi(cq), dtype=np.float64)
                 cp = cp + sgn * 0.5 * eps * cg
-                delta = 0.5 * np.sum(c * cp * cp) - lpl - H0
+                delta = 0.5 * kinetic2(c, cp) - lpl - H0
                 if not np.isfinite(delta) or delta > 1000:
                     return prop  # divergence: the subtree is discarded, the iteration ends
                 rhos = rhos + cp
@@ -520,8 +573,8 @@ class ChainSet:
         """What a resumed run must share with the saved one for the continuation to be bit-exact: model shape and
         arithmetic type, a hash of the data block, and the kernel's parameters."""
         m, k = self.model, self.kernel
-        par = {name: np.broadcast_to(np.asarray(v, dtype=np.float64), (m.p,) if np.ndim(v) else ()).copy()
-               for name, v in sorted(k.params.items())}
+        par = {name: np.broadcast_to(np.asarray(v, dtype=np.float64), ((m.p, m.p) if np.ndim(v) == 2 else (m.p,)) if np.ndim(v) else ()).copy()
+               for name, v in sorted(k.params.items())}  # (a dense NUTS kernel's inv_metric [p, p] among them)
         return {"kind": k.kind, "n": np.int64(m.n), "p": np.int64(m.p), "dtype": np.dtype(m.np_dtype).name,
                 "data_hash": m.data_hash, **{"param_" + name: v for name, v in par.items()}}
 

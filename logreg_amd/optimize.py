@@ -60,3 +60,13 @@ def overdispersed_init(beta_map, sd, chains, scale=2.0, seed=0):
     rng = np.random.Generator(np.random.Philox(seed))
     beta_map = np.asarray(beta_map, dtype=np.float64)
     return beta_map[None, :] + scale * np.asarray(sd)[None, :] * rng.standard_normal((int(chains), beta_map.shape[0]))
+
+
+def laplace_metric(model, beta_map):
+    """-> inv_metric [p, p]: the inverse of `lr_hessian`'s matrix at `beta_map` (the closed-form negative Hessian X^T W X +
+    diag(1 / pscale^2), float64, one pass over the rows) -- the covariance of the Laplace approximation, a dense metric for
+    `nutsKernel(..., inv_metric=)` / `nuts_warmup(metric="dense", inv_metric=, adapt_metric=False)` that needs no pilot run."""
+    _, _, H = model.hessian(np.asarray(beta_map, dtype=np.float64))
+    Lc = np.linalg.cholesky(0.5 * (H + H.T))  # the posterior is strictly log-concave: H is positive definite
+    Li = np.linalg.solve(Lc, np.eye(H.shape[0]))
+    return Li.T @ Li
