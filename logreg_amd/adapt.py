@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import AdaptInfo, AdaptOpts, RunOpts, check
-from .kernels import NUTS_COUNTERS, _model_of, nutsKernel
+from .kernels import NUTS_COUNTERS, _inv_metric_array, _model_of, nutsKernel
 
 TRACE_COLUMNS = ("eps", "accept_stat", "log_eps_bar", "window", "n")
 
@@ -51,17 +51,16 @@ def _dense_library(L=None):
         raise _lib.LogregHipError(f"this library has no dense-metric entry points (include/logreg_hip_dense.h): {e}") from e
 
 
-def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
-                chain_offset=0, keep=False):
-    """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
-
-    Returns an object with `eps`, `dmm`, `pre` (= 1 / dmm: BlackJAX's inverse mass matrix), `state` `[C, p]`, `kernel`
-    (`nutsKernel(lpost, glp, eps, dmm, max_depth)`, ready for `mcmc`), `trace` `[W, 5]` (columns `TRACE_COLUMNS`), `metric_trace`
-    `[windows, 2, p]` (var, dmm per window), `info` (the per-chain counters as `ChainSet.nuts_info` gives them, and `metric_skipped`,
-    `windows`, `seed`) and, with `keep=True`, `draws` `[W, C, p]`.  `lpost` and `glp` must be the closures of one `LogReg`."""
+def _warmup(who, symbols, library, start, shapes, finish, lpost, glp, init, num_warmup, target_accept, eps, max_depth, adapt_metric, seed, chain_offset,
+            keep):
+    """The body of `nuts_warmup` and `nuts_warmup_dense`: the checks, the start state and the seed, create / run / result / trace / destroy
+    and the result.  What differs comes as arguments: `who` names the caller in the error text, `symbols` is the prefix of the five entry
+    points in the binding `library`, `start(p)` checks the start metric and returns (`AdaptOpts.dmm0` or None, the further array
+    arguments of create), `shapes(p)` the shapes of the metric and of a window's row of `metric_trace`, `finish(res, metric, max_depth)`
+    adds the metric and the `kernel` to the result."""
     model = _model_of(lpost, "lpost")
     if model is None or _model_of(glp, "glp") is not model:
-        raise ValueError("nuts_warmup needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)")
+        raise ValueError(f"{who} needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)")
     W, max_depth = int(num_warmup), int(max_depth)
     if W < 1:
         raise ValueError(f"num_warmup must be >= 1, got {num_warmup}")
@@ -71,43 +70,63 @@ def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0
         raise ValueError(f"target_accept must be in (0, 1), got {target_accept}")
     if not (np.isfinite(eps) and float(eps) > 0):
         raise ValueError(f"eps must be finite and > 0, got {eps}")
-    dmm0 = np.ascontiguousarray(np.broadcast_to(np.asarray(dmm, dtype=np.float64), (model.p,)))
-    if not np.all(np.isfinite(dmm0) & (dmm0 > 0)):
-        raise ValueError("dmm must be finite and > 0")
+    p = model.p
+    dmm0, more = start(p)
     st = np.array(np.atleast_2d(np.asarray(init, dtype=np.float64)), dtype=model.np_dtype, order="C")
-    if st.ndim != 2 or st.shape[1] != model.p:
-        raise ValueError(f"init must be [p] or [C,p] with p={model.p}; got {np.shape(init)}")
+    if st.ndim != 2 or st.shape[1] != p:
+        raise ValueError(f"init must be [p] or [C,p] with p={p}; got {np.shape(init)}")
     Cn = st.shape[0]
-    L = _adapt_library(model._L)  # the library that made the model
+    L = library(model._L)  # the library that made the model
     _lib.require_gpu()
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
-    o = AdaptOpts(W=W, adapt_metric=int(bool(adapt_metric)), delta=float(target_accept), eps0=float(eps), dmm0=dmm0.ctypes.data)
+    seed = int(seed)
+    o = AdaptOpts(W=W, adapt_metric=int(bool(adapt_metric)), delta=float(target_accept), eps0=float(eps), dmm0=None if dmm0 is None else dmm0.ctypes.data)
     h = C.c_void_p()
-    check(L.lr_adapt_create(model.handle, Cn, C.byref(o), C.byref(h)))
+    check(getattr(L, symbols + "_create")(model.handle, Cn, C.byref(o), *(a.ctypes.data for a in more), C.byref(h)))
     try:
         counters = np.zeros(Cn, dtype=NUTS_COUNTERS)
-        draws = np.empty((W, Cn, model.p), dtype=model.np_dtype) if keep else None
-        opts = RunOpts(n_chains=Cn, chain_offset=int(chain_offset), thin=1, iters=1, seed=int(seed) & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO,
-                       on_device=0)
-        check(L.lr_adapt_run(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
+        draws = np.empty((W, Cn, p), dtype=model.np_dtype) if keep else None
+        opts = RunOpts(n_chains=Cn, chain_offset=int(chain_offset), thin=1, iters=1, seed=seed & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO, on_device=0)
+        check(getattr(L, symbols + "_run")(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
         e, info = C.c_double(), AdaptInfo()
-        dm = np.empty(model.p, dtype=np.float64)
-        check(L.lr_adapt_result(h, C.byref(e), dm.ctypes.data, C.byref(info)))
+        metric_shape, row_shape = shapes(p)
+        metric = np.empty(metric_shape, dtype=np.float64)
+        check(getattr(L, symbols + "_result")(h, C.byref(e), metric.ctypes.data, C.byref(info)))
         trace = np.zeros((W, _lib.ADAPT_TRACE_COLS), dtype=np.float64)
-        metric = np.zeros((info.n_windows, 2, model.p), dtype=np.float64)
-        check(L.lr_adapt_trace(h, trace.ctypes.data, metric.ctypes.data if info.n_windows else None))
+        metric_trace = np.zeros((info.n_windows, *row_shape), dtype=np.float64)
+        check(getattr(L, symbols + "_trace")(h, trace.ctypes.data, metric_trace.ctypes.data if info.n_windows else None))
     finally:
-        L.lr_adapt_destroy(h)
-    res = SimpleNamespace(eps=float(e.value), dmm=dm, pre=1.0 / dm, state=st.astype(np.float64), trace=trace, metric_trace=metric,
-                          kernel=nutsKernel(lpost, glp, float(e.value), dm, max_depth),
+        getattr(L, symbols + "_destroy")(h)
+    res = SimpleNamespace(eps=float(e.value), state=st.astype(np.float64), trace=trace, metric_trace=metric_trace,
                           info={"n_leapfrog": counters["n_leapfrog"].astype(np.int64), "divergent": counters["divergent"].astype(np.int64),
                                 "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
                                 "mean_accept_stat": counters["accept_stat_sum"] / W, "metric_skipped": int(info.metric_skipped),
-                                "windows": int(info.windows), "iterations": int(info.iterations), "seed": int(seed)})
+                                "windows": int(info.windows), "iterations": int(info.iterations), "seed": seed})
+    finish(res, metric, max_depth)
     if keep:
         res.draws = draws
     return res
+
+
+def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
+                chain_offset=0, keep=False):
+    """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
+
+    Returns an object with `eps`, `dmm`, `pre` (= 1 / dmm: BlackJAX's inverse mass matrix), `state` `[C, p]`, `kernel`
+    (`nutsKernel(lpost, glp, eps, dmm, max_depth)`, ready for `mcmc`), `trace` `[W, 5]` (columns `TRACE_COLUMNS`), `metric_trace`
+    `[windows, 2, p]` (var, dmm per window), `info` (the per-chain counters as `ChainSet.nuts_info` gives them, and `metric_skipped`,
+    `windows`, `seed`) and, with `keep=True`, `draws` `[W, C, p]`.  `lpost` and `glp` must be the closures of one `LogReg`."""
+    def start(p):
+        dmm0 = np.ascontiguousarray(np.broadcast_to(np.asarray(dmm, dtype=np.float64), (p,)))
+        if not np.all(np.isfinite(dmm0) & (dmm0 > 0)):
+            raise ValueError("dmm must be finite and > 0")
+        return dmm0, ()
+
+    def finish(res, dm, depth):
+        res.dmm, res.pre, res.kernel = dm, 1.0 / dm, nutsKernel(lpost, glp, res.eps, dm, depth)
+    return _warmup("nuts_warmup", "lr_adapt", _adapt_library, start, lambda p: ((p,), (2, p)), finish, lpost, glp, init, num_warmup, target_accept, eps,
+                   max_depth, adapt_metric, seed, chain_offset, keep)
 
 
 def nuts_warmup_dense(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, inv_metric=None, max_depth=10, adapt_metric=True, seed=None,
@@ -120,54 +139,13 @@ def nuts_warmup_dense(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, e
     Returns what `nuts_warmup` returns with `inv_metric` `[p, p]` in place of `dmm` / `pre`, `metric_trace` `[windows, p, p]` (the
     matrix after each window) and a dense `kernel` (`nutsKernel(lpost, glp, eps, max_depth=, inv_metric=res.inv_metric)`);
     `info["metric_skipped"]` counts the windows whose matrix was not positive definite (the previous one stays)."""
-    from .kernels import _inv_metric_array
-    model = _model_of(lpost, "lpost")
-    if model is None or _model_of(glp, "glp") is not model:
-        raise ValueError("nuts_warmup_dense needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)")
-    W, max_depth = int(num_warmup), int(max_depth)
-    if W < 1:
-        raise ValueError(f"num_warmup must be >= 1, got {num_warmup}")
-    if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
-        raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
-    if not 0.0 < float(target_accept) < 1.0:
-        raise ValueError(f"target_accept must be in (0, 1), got {target_accept}")
-    if not (np.isfinite(eps) and float(eps) > 0):
-        raise ValueError(f"eps must be finite and > 0, got {eps}")
-    st = np.array(np.atleast_2d(np.asarray(init, dtype=np.float64)), dtype=model.np_dtype, order="C")
-    if st.ndim != 2 or st.shape[1] != model.p:
-        raise ValueError(f"init must be [p] or [C,p] with p={model.p}; got {np.shape(init)}")
-    p, Cn = model.p, st.shape[0]
-    sig0 = np.eye(p) if inv_metric is None else _inv_metric_array(inv_metric, p)
-    if not np.all(np.isfinite(np.tril(sig0))):
-        raise ValueError("inv_metric must be finite")
-    target_accept, eps, adapt_metric, chain_offset = float(target_accept), float(eps), bool(adapt_metric), int(chain_offset)
-    L = _dense_library(model._L)  # the library that made the model
-    _lib.require_gpu()
-    if seed is None:
-        seed = int(np.random.randint(0, 2**31 - 1))
-    seed = int(seed)
-    o = AdaptOpts(W=W, adapt_metric=int(adapt_metric), delta=target_accept, eps0=eps, dmm0=None)
-    h = C.c_void_p()
-    check(L.lr_dense_adapt_create(model.handle, Cn, C.byref(o), sig0.ctypes.data, C.byref(h)))
-    try:
-        counters = np.zeros(Cn, dtype=NUTS_COUNTERS)
-        draws = np.empty((W, Cn, p), dtype=model.np_dtype) if keep else None
-        opts = RunOpts(n_chains=Cn, chain_offset=chain_offset, thin=1, iters=1, seed=seed & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO, on_device=0)
-        check(L.lr_dense_adapt_run(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
-        e, info = C.c_double(), AdaptInfo()
-        sig = np.empty((p, p), dtype=np.float64)
-        check(L.lr_dense_adapt_result(h, C.byref(e), sig.ctypes.data, C.byref(info)))
-        trace = np.zeros((W, _lib.ADAPT_TRACE_COLS), dtype=np.float64)
-        metric_trace = np.zeros((info.n_windows, p, p), dtype=np.float64)
-        check(L.lr_dense_adapt_trace(h, trace.ctypes.data, metric_trace.ctypes.data if info.n_windows else None))
-    finally:
-        L.lr_dense_adapt_destroy(h)
-    res = SimpleNamespace(eps=float(e.value), inv_metric=sig, state=st.astype(np.float64), trace=trace, metric_trace=metric_trace,
-                          kernel=nutsKernel(lpost, glp, float(e.value), max_depth=max_depth, inv_metric=sig),
-                          info={"n_leapfrog": counters["n_leapfrog"].astype(np.int64), "divergent": counters["divergent"].astype(np.int64),
-                                "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
-                                "mean_accept_stat": counters["accept_stat_sum"] / W, "metric_skipped": int(info.metric_skipped),
-                                "windows": int(info.windows), "iterations": int(info.iterations), "seed": seed})
-    if keep:
-        res.draws = draws
-    return res
+    def start(p):
+        sig0 = np.eye(p) if inv_metric is None else _inv_metric_array(inv_metric, p)
+        if not np.all(np.isfinite(np.tril(sig0))):
+            raise ValueError("inv_metric must be finite")
+        return None, (sig0,)
+
+    def finish(res, sig, depth):
+        res.inv_metric, res.kernel = sig, nutsKernel(lpost, glp, res.eps, max_depth=depth, inv_metric=sig)
+    return _warmup("nuts_warmup_dense", "lr_dense_adapt", _dense_library, start, lambda p: ((p, p), (p, p)), finish, lpost, glp, init, num_warmup, target_accept,
+                   eps, max_depth, adapt_metric, seed, chain_offset, keep)

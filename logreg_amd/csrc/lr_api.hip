@@ -7,7 +7,8 @@
 //   lr_adapt.h   the kernels of the NUTS warm-up (include/logreg_hip_adapt.h; its host side is the `NUTS warm-up` divider below)
 // The first half has one of each: check_opts() for the options of every call, run_request() for the front every lr_run_* shares (check,
 // plan_run(), nothing to do, device buffers or staged()), staged() for every call made with host pointers (run, NUTS, eval: allocate
-// what the call uses, copy in, launch on the NULL stream, the only hipDeviceSynchronize of the run path, copy back), and in
+// what the call uses, copy in, launch on the NULL stream, the only hipDeviceSynchronize of the run path, copy back), nuts_launch() for
+// every NUTS launch (lr_run_nuts, lr_run_nuts_dense and each warm-up iteration: the metric and the tuning block are its data), and in
 // lr_model_create one cleanup (a guard over lr_model_destroy), upload() for a device array and signed_rows() for the design, both
 // shared with lr_predict_create.
 // All arithmetic of the path runs in the kernels (lr_kernels.h, lr_mfma.h, lr_tall*.h, lr_wide*.h).
@@ -168,15 +169,35 @@ int run_common(lr_model* m, const RunSpec& rs, const lr_run_opts* o, void* state
 
 static_assert(sizeof(lr::NutsCounters) == sizeof(lr_nuts_counters), "lr_nuts_counters layout");
 
+// step and sqrt(dmm), eps / dmm, 1 / dmm of a diagonal metric, zero in padded coordinates: NutsArgs of a launch, the warm-up's NutsTune, HMC's RunSpec
 template <typename T, int P>
-int do_nuts_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
-              void* out, lr_nuts_counters* counters, int8_t* depth_out) {
-    auto ma = model_args<T, P>(m);
+void diag_tuning(int p, double eps, const double* dmm, T* step, T (&a)[P], T (&b)[P], T (&c)[P]) {
+    *step = (T)eps;
+    for (int j = 0; j < P; ++j) {
+        a[j] = j < p ? (T)std::sqrt(dmm[j]) : T(0);
+        b[j] = j < p ? (T)(eps / dmm[j]) : T(0);
+        c[j] = j < p ? (T)(1.0 / dmm[j]) : T(0);
+    }
+}
+
+// What differs between the NUTS launches, as data.  The metric: diagonal `dmm` (host), or a dense `factor` (device memory, lr_nuts_dense.h),
+// or neither where the tuning block holds it.  The warm-up: `tune` (device, NutsTune: step, and the diagonal metric) and `astat` [C].
+struct NutsMetric {
+    const double* dmm;
+    void* factor;
+    void* tune;
+    double* astat;
+    const char* who;  // prefix of the launch's error text
+};
+
+// the NutsArgs base every variant shares, from the model, the options and the arrays
+template <typename T, int P>
+lr::NutsArgs<T, P> nuts_args(const lr_model* m, const lr_run_opts* o, int max_depth, const RunArrays& d) {
     lr::NutsArgs<T, P> na{};
-    na.state = static_cast<T*>(state);
-    na.out = static_cast<T*>(out);
-    na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
-    na.depth_out = depth_out;
+    na.state = static_cast<T*>(d.state);
+    na.out = static_cast<T*>(d.out);
+    na.counters = static_cast<lr::NutsCounters*>(d.tally);
+    na.depth_out = d.depth_out;
     na.C = o->n_chains;
     na.chain_offset = o->chain_offset;
     na.iters = o->iters;
@@ -185,21 +206,30 @@ int do_nuts_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o,
     na.seed = o->seed;
     na.p = m->p;
     na.max_depth = max_depth;
-    na.step = (T)eps;
-    for (int j = 0; j < P; ++j) {  // sqrt(dmm), eps / dmm, 1 / dmm; zero in padded coordinates
-        na.a[j] = j < m->p ? (T)std::sqrt(dmm[j]) : T(0);
-        na.b[j] = j < m->p ? (T)(eps / dmm[j]) : T(0);
-        na.c[j] = j < m->p ? (T)(1.0 / dmm[j]) : T(0);
-    }
     na.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
-    lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
-    const int rc = m->table->launch_nuts(&cfg, o->n_chains, &ma, &na);
-    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return na;
+}
+
+// one NUTS launch of o->iters * o->thin iterations on `st`; every pointer of `d` and `mt` but dmm is device memory (eps: not read with mt.tune)
+template <typename T, int P>
+int nuts_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const NutsMetric& mt, const RunArrays& d) {
+    auto ma = model_args<T, P>(m);
+    lr::NutsArgs<T, P> na = nuts_args<T, P>(m, o, max_depth, d);
+    if (mt.dmm) diag_tuning(m->p, eps, mt.dmm, &na.step, na.a, na.b, na.c);
+    else if (!mt.tune) na.step = (T)eps;
+    const auto* tune = static_cast<const lr::NutsTune<T, P>*>(mt.tune);
+    const lr::NutsTunedArgs<T, P> tuned{na, tune, mt.astat};
+    const lr::NutsDenseArgs<T, P> dense{na, static_cast<const T*>(mt.factor)};
+    const lr::NutsDenseTunedArgs<T, P> dense_tuned{dense, tune, mt.astat};
+    const void* const args[] = {&na, &tuned, &dense, &dense_tuned};  // by lr::NutsVariant
+    const int variant = mt.factor ? (mt.tune ? lr::NUTS_DENSE_TUNED : lr::NUTS_DENSE) : (mt.tune ? lr::NUTS_DIAG_TUNED : lr::NUTS_DIAG);
+    const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const int rc = m->table->launch_nuts(&cfg, o->n_chains, &ma, args[variant], variant);
+    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "%sNUTS launch failed (%d): %s", mt.who, rc, hipGetErrorString(hipGetLastError()));
     return LR_OK;
 }
-int do_nuts(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const double* dmm, void* state,
-            void* out, lr_nuts_counters* counters, int8_t* depth_out) {
-    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_nuts_t, m, pl, st, o, eps, max_depth, dmm, state, out, counters, depth_out)
+int nuts_launch_any(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const NutsMetric& mt, const RunArrays& d) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, nuts_launch, m, pl, st, o, eps, max_depth, mt, d)
     return bad_width(m);
 }
 
@@ -253,44 +283,28 @@ int dense_factor_device(lr_model* m, hipStream_t st, const DenseFactorHost& f, v
     return LR_OK;
 }
 
-template <typename T, int P>
-int do_nuts_dense_t(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const void* factor, void* state,
-                    void* out, lr_nuts_counters* counters, int8_t* depth_out) {
-    auto ma = model_args<T, P>(m);
-    lr::NutsDenseArgs<T, P> na{};
-    na.state = static_cast<T*>(state);
-    na.out = static_cast<T*>(out);
-    na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
-    na.depth_out = depth_out;
-    na.C = o->n_chains;
-    na.chain_offset = o->chain_offset;
-    na.iters = o->iters;
-    na.thin = o->thin;
-    na.iter_offset = o->iter_offset;
-    na.seed = o->seed;
-    na.p = m->p;
-    na.max_depth = max_depth;
-    na.step = (T)eps;
-    na.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
-    na.factor = static_cast<const T*>(factor);
-    lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
-    const int rc = m->table->launch_nuts_dense(&cfg, o->n_chains, &ma, &na);
-    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "dense NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
-    return LR_OK;
-}
-int do_nuts_dense(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const DenseFactorHost& f, void* state,
-                  void* out, lr_nuts_counters* counters, int8_t* depth_out) {
-    void* factor = nullptr;
-    if (const int rc = dense_factor_device(m, st, f, &factor)) return rc;
-    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, do_nuts_dense_t, m, pl, st, o, eps, max_depth, factor, state, out, counters, depth_out)
-    return bad_width(m);
-}
-
 int positive_vec(const char* name, const double* v, int p) {
     if (!v) return fail(LR_ERR_INVALID, "%s is NULL", name);
     for (int j = 0; j < p; ++j)
         if (!(v[j] > 0) || !std::isfinite(v[j])) return fail(LR_ERR_INVALID, "%s[%d] must be finite and > 0", name, j);
     return LR_OK;
+}
+
+// The front lr_run_nuts and lr_run_nuts_dense share.  check() is the metric's own check, on the host, refused in this order: model, eps,
+// max_depth, metric, then what run_request refuses; metric(stream, &mt) names the metric of the launch on that stream.
+template <typename Check, typename Metric>
+int run_nuts(lr_model* m, int kind, double eps, int max_depth, const lr_run_opts* o, void* state, void* out, lr_nuts_counters* counters, int8_t* depth_out, Check&& check,
+             Metric&& metric) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
+    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
+    if (const int rc = check()) return rc;
+    return run_request(m, kind, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
+                           NutsMetric mt{nullptr, nullptr, nullptr, nullptr, ""};
+                           if (const int rc = metric(st, &mt)) return rc;
+                           return nuts_launch_any(m, pl, st, oo, eps, max_depth, mt, d);
+                       });
 }
 
 // signed rows  xs_i = s_i x_i  of a design X [n][p], zero-padded to P columns, in the compute dtype;  s_i = 2 y_i - 1, or 1 without labels
@@ -618,13 +632,8 @@ int lr_run_hmc(lr_model* m, void* state, double eps, int32_t l, const double* dm
     if (rc) return rc;
     RunSpec rs{};
     rs.kind = lr::KIND_HMC;
-    rs.step = eps;
     rs.l = l;
-    for (int j = 0; j < m->p; ++j) {
-        rs.a[j] = std::sqrt(dmm[j]);
-        rs.b[j] = eps / dmm[j];
-        rs.c[j] = 1.0 / dmm[j];
-    }
+    diag_tuning(m->p, eps, dmm, &rs.step, rs.a, rs.b, rs.c);
     return run_common(m, rs, o, state, nullptr, out, accepts);
 }
 
@@ -632,15 +641,11 @@ int lr_run_hmc(lr_model* m, void* state, double eps, int32_t l, const double* dm
 // exist, the run is one part (plan_nuts).
 int lr_run_nuts(lr_model* m, void* state, double eps, int32_t max_depth, const double* dmm, const lr_run_opts* o, void* out,
                 lr_nuts_counters* counters, int8_t* depth_out) {
-    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
-    if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
-    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
-    const int rc = positive_vec("dmm", dmm, m->p);
-    if (rc) return rc;
-    return run_request(m, LR_KIND_NUTS, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
-                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
-                           return do_nuts(m, pl, st, oo, eps, max_depth, dmm, d.state, d.out, static_cast<lr_nuts_counters*>(d.tally), d.depth_out);
-                       });
+    return run_nuts(m, LR_KIND_NUTS, eps, max_depth, o, state, out, counters, depth_out, [&] { return positive_vec("dmm", dmm, m->p); },
+                    [&](hipStream_t, NutsMetric* mt) {
+                        mt->dmm = dmm;
+                        return LR_OK;
+                    });
 }
 
 // NUTS under a dense metric (include/logreg_hip_dense.h): lr_run_nuts with the factor of inv_metric in place of dmm
@@ -653,15 +658,12 @@ int lr_dense_factor(int32_t p, const double* inv_metric, double* s, double* R, d
 
 int lr_run_nuts_dense(lr_model* m, void* state, double eps, int32_t max_depth, const double* inv_metric, const lr_run_opts* o, void* out,
                       lr_nuts_counters* counters, int8_t* depth_out) {
-    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
-    if (!(eps > 0) || !std::isfinite(eps)) return fail(LR_ERR_INVALID, "eps must be finite and > 0");
-    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
     DenseFactorHost f;
-    if (const int rc = dense_factor_host(m, "lr_run_nuts_dense", inv_metric, &f)) return rc;
-    return run_request(m, kKindNutsDense, max_depth, o, RunArrays{state, nullptr, out, counters, sizeof(lr_nuts_counters), depth_out},
-                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) {
-                           return do_nuts_dense(m, pl, st, oo, eps, max_depth, f, d.state, d.out, static_cast<lr_nuts_counters*>(d.tally), d.depth_out);
-                       });
+    return run_nuts(m, kKindNutsDense, eps, max_depth, o, state, out, counters, depth_out, [&] { return dense_factor_host(m, "lr_run_nuts_dense", inv_metric, &f); },
+                    [&](hipStream_t st, NutsMetric* mt) {
+                        mt->who = "dense ";
+                        return dense_factor_device(m, st, f, &mt->factor);
+                    });
 }
 
 int lr_hessian(lr_model* m, const double* beta, double* lpost, double* grad, double* hess, void* stream) {
@@ -1328,6 +1330,58 @@ void lr_cov_destroy(lr_cov* h) {
 
 // ---- NUTS warm-up: pooled step-size and metric adaptation (include/logreg_hip_adapt.h; kernels: lr_nuts.h TUNED, lr_adapt.h) ---------------
 }  // extern "C"
+namespace {
+// The dense metric of a warm-up (include/logreg_hip_dense.h "Warm-up"): the part of a handle that lr_dense_adapt_create adds, and the
+// steps it adds to the loop of adapt_enqueue
+struct DenseAdapt {
+    void* d_factor = nullptr;         // lr_nuts_dense.h `factor` of sigma
+    double* d_comoment = nullptr;     // with adapt_metric: the window's triple | the workgroups' triples [B] (lr_dense_adapt.h)
+    std::vector<double> sigma;        // the current inverse metric [p][p]
+    std::vector<double> sigma_trace;  // [n_windows][p][p]: Sigma after each window done
+    int64_t skipped = 0;              // windows whose Sigma was refused (the previous metric stays)
+    int windows = 0;
+    ~DenseAdapt() { free_all({d_factor, d_comoment}); }  // (lr_adapt_destroy has set the device)
+
+    // an iteration inside a window: the states [C][p] into the window's pooled co-moment (lr_dense_adapt.h), two launches on `st`
+    template <typename T, int P> int accumulate(hipStream_t st, const void* state, int64_t C, int64_t B, int p) {
+        double* part = d_comoment + lr::dense_triple_words(P);
+        hipLaunchKernelGGL((lr::k_dense_comoment_partial<T, P>), dim3((unsigned)B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), C, p, part);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL((lr::k_dense_comoment_merge<P>), dim3(1), dim3(P * P < 64 ? 64 : P * P), 0, st, part, B, p, d_comoment);
+        LR_HIP(hipGetLastError());
+        return LR_OK;
+    }
+    // The end of a window (lr_dense_adapt.h: dense_window_end): the one host synchronisation of the warm-up.  Reads the window's pooled triple, forms S = M / (n - 1) and
+    // Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I, factorises it and replaces the device factor; a Sigma that lr_dense_factor refuses keeps
+    // the previous metric and is counted.  The triple is emptied for the next window.
+    int window_end(const lr_model* m, hipStream_t st) {
+        const int p = m->p, P = m->P;
+        const size_t tw = (size_t)lr::dense_triple_words(P);
+        std::vector<double> win(tw);
+        LR_HIP(hipStreamSynchronize(st));
+        LR_HIP(hipMemcpy(win.data(), d_comoment, tw * sizeof(double), hipMemcpyDeviceToHost));
+        const double n = win[0];
+        std::vector<double> sig((size_t)p * p);
+        for (int j = 0; j < p; ++j)
+            for (int l = 0; l <= j; ++l) {
+                const double S = win[1 + P + (size_t)j * P + l] / (n - 1.0);
+                const double v = (n / (n + 5.0)) * S + (j == l ? 1e-3 * (5.0 / (n + 5.0)) : 0.0);
+                sig[(size_t)j * p + l] = sig[(size_t)l * p + j] = v;
+            }
+        DenseFactorHost f;
+        if (dense_factor_host(m, "lr_dense_adapt_run", sig.data(), &f) == LR_OK) {
+            LR_HIP(hipMemcpy(d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice));
+            sigma = sig;
+        } else {
+            ++skipped;
+        }
+        std::copy(sigma.begin(), sigma.end(), sigma_trace.begin() + (size_t)windows * p * p);
+        ++windows;
+        LR_HIP(hipMemsetAsync(d_comoment, 0, tw * sizeof(double), st));
+        return LR_OK;
+    }
+};
+}  // namespace
 struct lr_adapt {
     lr_model* m = nullptr;
     int64_t C = 0, B = 0;  // chains, workgroups of k_adapt_partial
@@ -1343,14 +1397,7 @@ struct lr_adapt {
     double* d_fixed = nullptr;
     size_t words = 0, tune_bytes = 0;
     Workspace st_state, st_out, st_tally, st_depth, st_astat;  // a call made with host pointers stages its arrays here
-    // lr_dense_adapt_create (include/logreg_hip_dense.h): the iterations run k_nuts_dense under d_factor (lr_nuts_dense.h `factor`)
-    void* d_factor = nullptr;
-    bool dense_metric = false;     // adapt_metric: the windows re-estimate Sigma (dense_window_end)
-    double* d_comoment = nullptr;  // the window's triple | the workgroups' triples [B] (lr_dense_adapt.h)
-    std::vector<double> sigma;     // the current inverse metric [p][p]
-    std::vector<double> sigma_trace;  // [n_windows][p][p]: Sigma after each window done
-    int64_t dense_skipped = 0;     // windows whose Sigma was refused (the previous metric stays)
-    int dense_windows = 0;
+    std::unique_ptr<DenseAdapt> dense;  // lr_dense_adapt_create: the iterations run k_nuts_dense under dense->d_factor
     int p() const { return m->p; }
     size_t o_dmm() const { return 8; }
     size_t o_win() const { return o_dmm() + (size_t)p(); }
@@ -1389,111 +1436,53 @@ int adapt_windows(int W, int init, int term, int base, int* ends, int* init_out)
     return n;
 }
 
-// the NutsTune block of (eps, dmm), formed as do_nuts_t forms NutsArgs
+// the NutsTune block of (eps, dmm) a warm-up starts from
 template <typename T, int P>
-int adapt_tune_image(int p, double eps, const double* dmm, std::vector<unsigned char>* img) {
+int tune_start(int p, double eps, const double* dmm, std::vector<unsigned char>* img) {
     lr::NutsTune<T, P> t{};
-    t.step = (T)eps;
-    for (int j = 0; j < P; ++j) {
-        t.a[j] = j < p ? (T)std::sqrt(dmm[j]) : T(0);
-        t.b[j] = j < p ? (T)(eps / dmm[j]) : T(0);
-        t.c[j] = j < p ? (T)(1.0 / dmm[j]) : T(0);
-    }
+    diag_tuning(p, eps, dmm, &t.step, t.a, t.b, t.c);
     img->resize(sizeof(t));
     std::memcpy(img->data(), &t, sizeof(t));
     return LR_OK;
 }
-
-// The end of a dense metric's window (include/logreg_hip_dense.h "Warm-up"): the one host synchronisation of the warm-up.  Reads the
-// window's pooled triple, forms S = M / (n - 1) and Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I, factorises it and replaces the device
-// factor; a Sigma that lr_dense_factor refuses keeps the previous metric and is counted.  The triple is emptied for the next window.
-int dense_window_end(lr_adapt* h, hipStream_t st, int P) {
-    const int p = h->p();
-    const size_t tw = (size_t)lr::dense_triple_words(P);
-    std::vector<double> win(tw);
-    LR_HIP(hipStreamSynchronize(st));
-    LR_HIP(hipMemcpy(win.data(), h->d_comoment, tw * sizeof(double), hipMemcpyDeviceToHost));
-    const double n = win[0];
-    std::vector<double> sig((size_t)p * p);
-    for (int j = 0; j < p; ++j)
-        for (int l = 0; l <= j; ++l) {
-            const double S = win[1 + P + (size_t)j * P + l] / (n - 1.0);
-            const double v = (n / (n + 5.0)) * S + (j == l ? 1e-3 * (5.0 / (n + 5.0)) : 0.0);
-            sig[(size_t)j * p + l] = sig[(size_t)l * p + j] = v;
-        }
-    DenseFactorHost f;
-    if (dense_factor_host(h->m, "lr_dense_adapt_run", sig.data(), &f) == LR_OK) {
-        LR_HIP(hipMemcpy(h->d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice));
-        h->sigma = sig;
-    } else {
-        ++h->dense_skipped;
-    }
-    std::copy(h->sigma.begin(), h->sigma.end(), h->sigma_trace.begin() + (size_t)h->dense_windows * p * p);
-    ++h->dense_windows;
-    LR_HIP(hipMemsetAsync(h->d_comoment, 0, tw * sizeof(double), st));
-    return LR_OK;
+int tune_start_any(const lr_model* m, double eps, const double* dmm, std::vector<unsigned char>* img) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, tune_start, m->p, eps, dmm, img)
+    return bad_width(m);
 }
 
-// `iters` iterations, three launches each, on `st`; every pointer is device memory
+// `iters` iterations on `st`: the tuned NUTS launch, the pooled partials, the update; the handle's dense part adds its co-moments inside a
+// window and its window end.  Every pointer is device memory; `o` has iters = thin = 1 and no statistics (lr_adapt_run).
 template <typename T, int P>
 int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
                   int8_t* depth_out, double* astat_out, int64_t iters) {
     lr_model* m = h->m;
-    auto ma = model_args<T, P>(m);
-    const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_NUTS, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    DenseAdapt* dense = h->dense.get();
     const lr::AdaptDev dev = h->dev();
     auto* tune = static_cast<lr::NutsTune<T, P>*>(h->tune());
     const size_t row = (size_t)h->C * m->p;
     h->last = st;
     for (int64_t i = 0; i < iters; ++i) {
-        lr::NutsTunedArgs<T, P> na{};
-        na.state = static_cast<T*>(state);
-        na.out = out ? static_cast<T*>(out) + (size_t)i * row : nullptr;
-        na.counters = reinterpret_cast<lr::NutsCounters*>(counters);
-        na.depth_out = depth_out ? depth_out + (size_t)i * h->C : nullptr;
-        na.C = h->C;
-        na.chain_offset = o->chain_offset;
-        na.iters = 1;
-        na.thin = 1;
-        na.iter_offset = LR_ADAPT_ITER_BASE + h->t;
-        na.seed = o->seed;
-        na.p = m->p;
-        na.max_depth = max_depth;
-        na.stats = lr::StatsArgs{nullptr, 1, 0};
-        na.tune = tune;
-        na.astat = astat_out ? astat_out + (size_t)i * h->C : h->astat();
-        int rc;
-        if (h->d_factor) {  // the same iteration under the handle's dense metric: `step` alone comes from the tuning block
-            lr::NutsDenseTunedArgs<T, P> nd{};
-            static_cast<lr::NutsArgs<T, P>&>(nd) = na;
-            nd.factor = static_cast<const T*>(h->d_factor);
-            nd.tune = na.tune;
-            nd.astat = na.astat;
-            rc = m->table->launch_nuts_dense_tuned(&cfg, h->C, &ma, &nd);
-        } else {
-            rc = m->table->launch_nuts_tuned(&cfg, h->C, &ma, &na);
-        }
-        if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "lr_adapt_run: NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+        lr_run_opts it = *o;
+        it.iter_offset = LR_ADAPT_ITER_BASE + h->t;
+        const NutsMetric mt{nullptr, dense ? dense->d_factor : nullptr, tune, astat_out ? astat_out + (size_t)i * h->C : h->astat(), "lr_adapt_run: "};
+        const RunArrays d{state, nullptr, out ? static_cast<T*>(out) + (size_t)i * row : nullptr, counters, sizeof(lr_nuts_counters),
+                          depth_out ? depth_out + (size_t)i * h->C : nullptr};
+        if (const int rc = nuts_launch<T, P>(m, pl, st, &it, 0.0, max_depth, mt, d)) return rc;
         const bool in_window = h->window < h->n_windows && h->t >= (h->window ? h->ends[h->window - 1] : h->init);
         const bool window_end = in_window && h->t == h->ends[h->window] - 1;
-        hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), na.astat, h->C, m->p, in_window ? 1 : 0,
+        hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), mt.astat, h->C, m->p, in_window ? 1 : 0,
                            dev.partial);
         LR_HIP(hipGetLastError());
-        if (h->dense_metric && in_window) {  // the pooled co-moment of the dense metric's window (lr_dense_adapt.h)
-            double* part = h->d_comoment + lr::dense_triple_words(P);
-            hipLaunchKernelGGL((lr::k_dense_comoment_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), h->C, m->p, part);
-            LR_HIP(hipGetLastError());
-            hipLaunchKernelGGL((lr::k_dense_comoment_merge<P>), dim3(1), dim3(P * P < 64 ? 64 : P * P), 0, st, part, h->B, m->p, h->d_comoment);
-            LR_HIP(hipGetLastError());
-        }
+        if (dense && in_window)
+            if (const int rc = dense->accumulate<T, P>(st, state, h->C, h->B, m->p)) return rc;
         const lr::AdaptStep s{h->C, h->t, m->p, h->m_since + 1, in_window ? h->window : -1, window_end ? 1 : 0, h->t == h->W - 1 ? 1 : 0, h->delta, h->gamma, h->t0, h->kappa};
         hipLaunchKernelGGL((lr::k_adapt_update<T, P>), dim3(1), dim3(64), 0, st, dev, s, tune);
         LR_HIP(hipGetLastError());
         ++h->t;
         h->m_since = window_end ? 0 : h->m_since + 1;
         if (window_end) ++h->window;
-        if (h->dense_metric && window_end)
-            if (const int rcw = dense_window_end(h, st, P)) return rcw;
+        if (dense && window_end)
+            if (const int rc = dense->window_end(m, st)) return rc;
     }
     return LR_OK;
 }
@@ -1510,9 +1499,30 @@ int adapt_enqueue_checked(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_
     if (rc != LR_OK) h->failed = true;
     return rc;
 }
-int adapt_tune_image_any(const lr_model* m, double eps, const double* dmm, std::vector<unsigned char>* img) {
-    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, adapt_tune_image, m->p, eps, dmm, img)
-    return bad_width(m);
+
+// what lr_adapt_result and lr_dense_adapt_result report: the step size, the metric (`dense`: its Sigma and window counts, else the handle's dmm
+// and the device's counts) and the counts
+int adapt_result(lr_adapt* h, const DenseAdapt* dense, double* eps, double* metric, lr_adapt_info* info) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_result: handle is NULL");
+    LR_HIP(hipSetDevice(h->m->device));
+    LR_HIP(hipStreamSynchronize(h->last));
+    double da[8];
+    LR_HIP(hipMemcpy(da, h->d_fixed, sizeof(da), hipMemcpyDeviceToHost));
+    if (eps) *eps = da[lr::AD_EPS_REPORT];
+    if (metric && dense) std::copy(dense->sigma.begin(), dense->sigma.end(), metric);
+    else if (metric) LR_HIP(hipMemcpy(metric, h->d_fixed + h->o_dmm(), (size_t)h->p() * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) *info = lr_adapt_info{h->t, dense ? dense->skipped : (int64_t)da[lr::AD_SKIPPED], dense ? dense->windows : (int32_t)da[lr::AD_WINDOWS], h->n_windows};
+    return LR_OK;
+}
+// ... and the traces: [W][5], and the metric after each window (dmm: [windows][2][p] from the device; dense: [windows][p][p])
+int adapt_trace(lr_adapt* h, const DenseAdapt* dense, double* trace, double* metric) {
+    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_trace: handle is NULL");
+    LR_HIP(hipSetDevice(h->m->device));
+    LR_HIP(hipStreamSynchronize(h->last));
+    if (trace) LR_HIP(hipMemcpy(trace, h->d_fixed + h->o_trace(), (size_t)h->W * LR_ADAPT_TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    if (metric && dense) std::copy(dense->sigma_trace.begin(), dense->sigma_trace.end(), metric);
+    else if (metric && h->n_windows > 0) LR_HIP(hipMemcpy(metric, h->d_fixed + h->o_metric(), (size_t)h->n_windows * 2 * h->p() * sizeof(double), hipMemcpyDeviceToHost));
+    return LR_OK;
 }
 }  // namespace
 extern "C" {
@@ -1539,7 +1549,7 @@ int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** o
         if (!(v >= 0) || !std::isfinite(v)) return fail(LR_ERR_INVALID, "lr_adapt_create: gamma, t0 and kappa must be finite and > 0, 0 for the defaults (got %g)", v);
     if (o->dmm0)
         if (const int rc = positive_vec("lr_adapt_create: dmm0", o->dmm0, m->p)) return rc;
-    if (m->P > 32 || !m->table || !m->table->launch_nuts_tuned)
+    if (m->P > 32 || !m->table || !m->table->launch_nuts)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
     if (const int rc = use_device(m->device, "lr_adapt_create")) return rc;
     std::unique_ptr<lr_adapt> h(new lr_adapt());
@@ -1557,7 +1567,7 @@ int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** o
     std::vector<double> dmm((size_t)m->p, 1.0);
     if (o->dmm0) std::copy(o->dmm0, o->dmm0 + m->p, dmm.begin());
     std::vector<unsigned char> tune;
-    if (const int rc = adapt_tune_image_any(m, eps0, dmm.data(), &tune)) return rc;
+    if (const int rc = tune_start_any(m, eps0, dmm.data(), &tune)) return rc;
     h->tune_bytes = tune.size();
     h->words = h->o_tune();
     const size_t want = h->words * sizeof(double) + h->tune_bytes;
@@ -1585,15 +1595,17 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
     if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "lr_adapt_run: max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
     if (o->n_chains != h->C) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->n_chains must be the handle's %lld chains (got %lld)", (long long)h->C, (long long)o->n_chains);
     if (o->stats) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->stats must be NULL (a warm-up keeps no streaming statistics)");
-    lr_run_opts oo = *o;  // iters, thin and iter_offset are the warm-up's own
+    lr_run_opts oo = *o;  // iters, thin and iter_offset are the warm-up's own (adapt_enqueue), the fields of the absent statistics as its launches have them
     oo.iters = 1;
     oo.thin = 1;
     oo.iter_offset = 0;
+    oo.stats_batch = 1;
+    oo.stats_first = 0;
     lr_model* m = h->m;
     if (const int rc = check_opts(m, &oo, true)) return rc;
     LR_HIP(hipSetDevice(m->device));
     Plan pl;
-    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl, h->d_factor != nullptr)) return rc;
+    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl, h->dense != nullptr)) return rc;
     if (iters == 0) return LR_OK;
     if (oo.on_device) return adapt_enqueue_checked(h, pl, (hipStream_t)oo.stream, &oo, max_depth, state, out, counters, depth_out, astat_out, iters);
     const size_t C = (size_t)h->C, sbytes = C * m->p * m->esize();
@@ -1618,32 +1630,15 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
     return LR_OK;
 }
 
-int lr_adapt_result(lr_adapt* h, double* eps, double* dmm, lr_adapt_info* info) {
-    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_result: handle is NULL");
-    LR_HIP(hipSetDevice(h->m->device));
-    LR_HIP(hipStreamSynchronize(h->last));
-    double da[8];
-    LR_HIP(hipMemcpy(da, h->d_fixed, sizeof(da), hipMemcpyDeviceToHost));
-    if (eps) *eps = da[lr::AD_EPS_REPORT];
-    if (dmm) LR_HIP(hipMemcpy(dmm, h->d_fixed + h->o_dmm(), (size_t)h->p() * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) *info = lr_adapt_info{h->t, (int64_t)da[lr::AD_SKIPPED], (int32_t)da[lr::AD_WINDOWS], h->n_windows};
-    return LR_OK;
-}
+int lr_adapt_result(lr_adapt* h, double* eps, double* dmm, lr_adapt_info* info) { return adapt_result(h, nullptr, eps, dmm, info); }
 
-int lr_adapt_trace(lr_adapt* h, double* trace, double* metric) {
-    if (!h) return fail(LR_ERR_INVALID, "lr_adapt_trace: handle is NULL");
-    LR_HIP(hipSetDevice(h->m->device));
-    LR_HIP(hipStreamSynchronize(h->last));
-    if (trace) LR_HIP(hipMemcpy(trace, h->d_fixed + h->o_trace(), (size_t)h->W * LR_ADAPT_TRACE_COLS * sizeof(double), hipMemcpyDeviceToHost));
-    if (metric && h->n_windows > 0) LR_HIP(hipMemcpy(metric, h->d_fixed + h->o_metric(), (size_t)h->n_windows * 2 * h->p() * sizeof(double), hipMemcpyDeviceToHost));
-    return LR_OK;
-}
+int lr_adapt_trace(lr_adapt* h, double* trace, double* metric) { return adapt_trace(h, nullptr, trace, metric); }
 
 void lr_adapt_destroy(lr_adapt* h) {
     if (!h) return;
     (void)hipSetDevice(h->m->device);
-    free_all({h->d_fixed, h->st_state.p, h->st_out.p, h->st_tally.p, h->st_depth.p, h->st_astat.p, h->d_factor, h->d_comoment});
-    delete h;
+    free_all({h->d_fixed, h->st_state.p, h->st_out.p, h->st_tally.p, h->st_depth.p, h->st_astat.p});
+    delete h;  // (and with it the dense part and its two buffers)
 }
 
 // the warm-up under a dense metric (include/logreg_hip_dense.h): an lr_adapt whose iterations run k_nuts_dense and whose windows, with
@@ -1662,27 +1657,28 @@ int lr_dense_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, const 
     }
     DenseFactorHost f;
     if (const int rc = dense_factor_host(m, "lr_dense_adapt_create", sigma.data(), &f)) return rc;
-    if (!m->table || !m->table->launch_nuts_dense_tuned) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
+    if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
     lr_adapt* h = nullptr;
     if (const int rc = lr_adapt_create(m, C, o, &h)) return rc;
-    h->dense_metric = h->n_windows > 0;
-    h->sigma = sigma;
-    h->sigma_trace.assign((size_t)h->n_windows * p * p, 0.0);
+    h->dense.reset(new DenseAdapt());
+    DenseAdapt* d = h->dense.get();
+    d->sigma = sigma;
+    d->sigma_trace.assign((size_t)h->n_windows * p * p, 0.0);
     const size_t cm_bytes = (size_t)(h->B + 1) * lr::dense_triple_words(m->P) * sizeof(double);
-    hipError_t e = hipMalloc(&h->d_factor, f.image.size());
-    if (e != hipSuccess) h->d_factor = nullptr;
-    if (e == hipSuccess && h->dense_metric) {
-        e = hipMalloc((void**)&h->d_comoment, cm_bytes);
-        if (e != hipSuccess) h->d_comoment = nullptr;
+    hipError_t e = hipMalloc(&d->d_factor, f.image.size());
+    if (e != hipSuccess) d->d_factor = nullptr;
+    if (e == hipSuccess && h->n_windows > 0) {  // adapt_metric: the windows re-estimate Sigma
+        e = hipMalloc((void**)&d->d_comoment, cm_bytes);
+        if (e != hipSuccess) d->d_comoment = nullptr;
     }
     if (e != hipSuccess) {
         lr_adapt_destroy(h);
         return fail(LR_ERR_NOMEM, "lr_dense_adapt_create: allocating the metric's factor and co-moments failed");
     }
-    e = hipMemcpy(h->d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && h->d_comoment) {  // an empty window
+    e = hipMemcpy(d->d_factor, f.image.data(), f.image.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && d->d_comoment) {  // an empty window
         const std::vector<double> zero((size_t)lr::dense_triple_words(m->P), 0.0);
-        e = hipMemcpy(h->d_comoment, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice);
+        e = hipMemcpy(d->d_comoment, zero.data(), zero.size() * sizeof(double), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         lr_adapt_destroy(h);
@@ -1693,24 +1689,16 @@ int lr_dense_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, const 
 }
 int lr_dense_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters,
                        int8_t* depth_out, double* astat_out) {
-    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_run: the handle is not one of lr_dense_adapt_create");
+    if (h && !h->dense) return fail(LR_ERR_INVALID, "lr_dense_adapt_run: the handle is not one of lr_dense_adapt_create");
     return lr_adapt_run(h, state, iters, max_depth, o, out, counters, depth_out, astat_out);
 }
 int lr_dense_adapt_result(lr_adapt* h, double* eps, double* inv_metric, lr_adapt_info* info) {
-    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_result: the handle is not one of lr_dense_adapt_create");
-    if (const int rc = lr_adapt_result(h, eps, nullptr, info)) return rc;
-    if (inv_metric) std::copy(h->sigma.begin(), h->sigma.end(), inv_metric);
-    if (info) {
-        info->metric_skipped = h->dense_skipped;
-        info->windows = h->dense_windows;
-    }
-    return LR_OK;
+    if (h && !h->dense) return fail(LR_ERR_INVALID, "lr_dense_adapt_result: the handle is not one of lr_dense_adapt_create");
+    return adapt_result(h, h ? h->dense.get() : nullptr, eps, inv_metric, info);
 }
 int lr_dense_adapt_trace(lr_adapt* h, double* trace, double* metric) {
-    if (h && !h->d_factor) return fail(LR_ERR_INVALID, "lr_dense_adapt_trace: the handle is not one of lr_dense_adapt_create");
-    if (const int rc = lr_adapt_trace(h, trace, nullptr)) return rc;
-    if (metric) std::copy(h->sigma_trace.begin(), h->sigma_trace.end(), metric);
-    return LR_OK;
+    if (h && !h->dense) return fail(LR_ERR_INVALID, "lr_dense_adapt_trace: the handle is not one of lr_dense_adapt_create");
+    return adapt_trace(h, h ? h->dense.get() : nullptr, trace, metric);
 }
 void lr_dense_adapt_destroy(lr_adapt* h) { lr_adapt_destroy(h); }
 

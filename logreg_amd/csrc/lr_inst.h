@@ -54,6 +54,10 @@ template <auto Kernel> inline hipError_t allow_lds(size_t dynamic_bytes) {
 
 struct Variant { int mode, G, R; };
 
+// The kernel InstTable::launch_nuts launches and its argument struct.  The metric: k_nuts (lr_nuts.h, NutsArgs) or k_nuts_dense
+// (lr_nuts_dense.h, NutsDenseArgs); TUNED: the step, and the diagonal metric, from a device block (the warm-up: Nuts[Dense]TunedArgs)
+enum NutsVariant { NUTS_DIAG, NUTS_DIAG_TUNED, NUTS_DENSE, NUTS_DENSE_TUNED };
+
 struct InstTable {
     int dtype;  // LR_F32 / LR_F64
     int P;      // padded parameter width
@@ -71,14 +75,9 @@ struct InstTable {
     // this width) and the one-off build into `store`; may be null
     size_t (*mfma_image_bytes)(int64_t n);
     int (*launch_mfma_image)(hipStream_t, const void* rows, int64_t n, void* store);
-    // NUTS (lr_nuts.h), rows in LDS on 16 lanes per chain; `nuts_args` is a NutsArgs<T,P>; null where no such kernel exists
-    int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
-    // ... and its TUNED instantiation, step and metric from a device block (the warm-up, lr_adapt.h); `nuts_args` is a NutsTunedArgs<T,P>
-    int (*launch_nuts_tuned)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
-    // NUTS under a dense metric (lr_nuts_dense.h); `nuts_args` is a NutsDenseArgs<T,P> / NutsDenseTunedArgs<T,P>; cfg->lds_bytes = rows +
-    // checkpoints + the two matrices
-    int (*launch_nuts_dense)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
-    int (*launch_nuts_dense_tuned)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args);
+    // NUTS, rows in LDS on 16 lanes per chain; `nuts_args` is the argument struct of `variant` (a NutsVariant); cfg->lds_bytes = rows +
+    // checkpoints, + the two matrices under a dense metric; null where the width has no NUTS kernel
+    int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args, int variant);
 };
 
 }  // namespace lr

@@ -284,39 +284,24 @@ int launch_tall_update(hipStream_t st, int kind, int phase, int64_t iter, int64_
     return check(hipGetLastError());
 }
 
-// NUTS: one kernel per (dtype, padded p), rows in LDS, 16 lanes per chain (lr_nuts.h); cfg->lds_bytes = rows + checkpoints
-int launch_nuts(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
-    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
-    const auto& a = *static_cast<const NutsArgs<T, P>*>(nuts_args);
-    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
-    return launch_capped<&k_nuts<T, P, MODE_LDS, 0>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
+// NUTS: one kernel per (dtype, padded p) and variant, rows in LDS, 16 lanes per chain (lr_nuts.h; under a dense metric lr_nuts_dense.h);
+// cfg->lds_bytes = rows + checkpoints (+ the dense metric's two matrices)
+template <auto Kernel, typename Args> int launch_nuts_v(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
+    return launch_capped<Kernel>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, *static_cast<const ModelArgs<T, P>*>(model_args), *static_cast<const Args*>(nuts_args));
 }
-
-int launch_nuts_tuned(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
-    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
-    const auto& a = *static_cast<const NutsTunedArgs<T, P>*>(nuts_args);
+int launch_nuts(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args, int variant) {
     if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
-    return launch_capped<&k_nuts<T, P, MODE_LDS, 0, true>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
-}
-
-// ... and under a dense metric (lr_nuts_dense.h)
-int launch_nuts_dense(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
-    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
-    const auto& a = *static_cast<const NutsDenseArgs<T, P>*>(nuts_args);
-    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
-    return launch_capped<&k_nuts_dense<T, P, MODE_LDS, 0>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
-}
-
-int launch_nuts_dense_tuned(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* nuts_args) {
-    const auto& m = *static_cast<const ModelArgs<T, P>*>(model_args);
-    const auto& a = *static_cast<const NutsDenseTunedArgs<T, P>*>(nuts_args);
-    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
-    return launch_capped<&k_nuts_dense<T, P, MODE_LDS, 0, true>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, m, a);
+    switch (variant) {
+    case NUTS_DIAG: return launch_nuts_v<&k_nuts<T, P, MODE_LDS, 0>, NutsArgs<T, P>>(cfg, C, model_args, nuts_args);
+    case NUTS_DIAG_TUNED: return launch_nuts_v<&k_nuts<T, P, MODE_LDS, 0, true>, NutsTunedArgs<T, P>>(cfg, C, model_args, nuts_args);
+    case NUTS_DENSE: return launch_nuts_v<&k_nuts_dense<T, P, MODE_LDS, 0>, NutsDenseArgs<T, P>>(cfg, C, model_args, nuts_args);
+    case NUTS_DENSE_TUNED: return launch_nuts_v<&k_nuts_dense<T, P, MODE_LDS, 0, true>, NutsDenseTunedArgs<T, P>>(cfg, C, model_args, nuts_args);
+    default: return -1;
+    }
 }
 
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_nuts_tuned,
-                          &launch_nuts_dense, &launch_nuts_dense_tuned};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts};
 
 }  // namespace
 }  // namespace lr

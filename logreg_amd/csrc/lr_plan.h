@@ -541,7 +541,7 @@ int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, 
     if (bytes > kLdsBudget)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes) and the U-turn checkpoints need %zu bytes of LDS, beyond the %zu a "
                     "workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n, lds_rows_bytes(m), bytes, kLdsBudget);
-    if (!m->table || !m->table->launch_nuts || (dense && !m->table->launch_nuts_dense)) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
+    if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
     *out = Plan{lr::MODE_LDS, 16, 0, bytes};
     return LR_OK;
 }

@@ -214,6 +214,41 @@ def test_nuts_warmup_validates_before_any_device_access(pima, pscale):
     assert params["num_warmup"].default == 1000 and params["target_accept"].kind is inspect.Parameter.KEYWORD_ONLY and params["eps"].default == 1.0
 
 
+def test_both_warmups_keep_their_error_texts(pima, pscale):
+    """nuts_warmup and nuts_warmup_dense share one body: every refusal of an argument is worded as each of them worded it, the function's
+    own name included, and is raised before any device access (the test double has no warm-up entry point)."""
+    import logreg_amd as la
+    import twin
+    from logreg_amd import _lib
+    X, y = pima
+    twin.install()
+    try:
+        model = la.LogReg(X, y, pscale, dtype="float64")
+        init = np.zeros((6, 8))
+        fused = " needs a fused kernel: lpost and glp must be the closures of one LogReg (the generic NumPy NUTS has no warm-up)"
+        shared = [(dict(num_warmup=0), "num_warmup must be >= 1, got 0"), (dict(max_depth=0), f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got 0"),
+                  (dict(target_accept=1), "target_accept must be in (0, 1), got 1"), (dict(eps=0), "eps must be finite and > 0, got 0"),
+                  (dict(init=np.zeros((6, 7))), "init must be [p] or [C,p] with p=8; got (6, 7)")]
+        own = {"nuts_warmup": [(dict(dmm=[1.0] * 7 + [np.nan]), "dmm must be finite and > 0"), (dict(dmm=np.inf), "dmm must be finite and > 0")],
+               "nuts_warmup_dense": [(dict(inv_metric=np.ones((8, 7))), "inv_metric must be a square matrix [p, p] with p=8; got (8, 7)"),
+                                     (dict(inv_metric=np.full((8, 8), np.nan)), "inv_metric must be finite")]}
+        for name, cases_of in own.items():
+            warm = getattr(la, name)
+            for glp in (lambda b: -b, model.lpost):
+                with pytest.raises(ValueError) as e:
+                    warm(model.lpost, glp, init, 10)
+                assert str(e.value) == name + fused
+            for bad, text in shared + cases_of:
+                kw = dict(init=init, num_warmup=10)
+                kw.update(bad)
+                with pytest.raises(ValueError) as e:
+                    warm(model.lpost, model.glp, **kw)
+                assert str(e.value) == text, (name, bad)
+        model.close()
+    finally:
+        twin.uninstall()
+
+
 def test_host_side_of_the_warmup_under_asan_and_ubsan(tmp_path):
     """tests/host/adapt_harness.cpp, a program of its own, linked with tests/host/hip_stub.cpp, lr_api.hip and the library's instantiation
     objects exactly as tests/test_cov_cpu.py links the covariance harness."""
