@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, "lib", "liblogreg_hip.so")
 LR_F32, LR_F64 = 0, 1
 STATS_ROWS = 7  # LR_STATS_ROWS
 PREC_BY_NAME = {"auto": 0, "full": 1, "bf16": 2}  # LR_PREC_*
-KIND_BY_NAME = {"rwmh": 0, "mala": 1, "hmc": 2, "ul": 3, "nuts": 4}  # LR_KIND_* (LR_KIND_NUTS: include/logreg_hip_nuts.h)
+KIND_BY_NAME = {"rwmh": 0, "mala": 1, "hmc": 2, "ul": 3, "nuts": 4, "pg": 6}  # LR_KIND_* (LR_KIND_NUTS: include/logreg_hip_nuts.h, LR_KIND_PG: logreg_hip_pg.h)
 NUTS_MAX_DEPTH = 10  # LR_NUTS_MAX_DEPTH
 MODE_AUTO, MODE_REG, MODE_LDS, MODE_GLOBAL, MODE_MFMA, MODE_STEPWISE, MODE_MIXED = -1, 0, 1, 2, 3, 4, 5
 MODE_NAMES = {MODE_REG: "reg", MODE_LDS: "lds", MODE_GLOBAL: "global", MODE_MFMA: "mfma", MODE_STEPWISE: "stepwise", MODE_MIXED: "mixed"}
@@ -193,8 +193,22 @@ DENSE_SYMBOLS = {
     "lr_dense_adapt_destroy": (None, [_vp]),
 }
 
+class PgCounters(C.Structure):  # lr_pg_counters (include/logreg_hip_pg.h)
+    _fields_ = [("proposals", C.c_uint64), ("series_terms", C.c_uint64), ("skipped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PG_TAG = 0x10000000  # LR_PG_TAG
+PG_MAX_ROWS = 65536  # LR_PG_MAX_ROWS
+# name -> (restype, argtypes); every symbol include/logreg_hip_pg.h declares.  A table of its own like DENSE_SYMBOLS, bound on first use
+# (load_pg)
+PG_SYMBOLS = {
+    "lr_run_pg": (C.c_int, [_vp, _vp, _op, _vp, _vp]),
+    "lr_pg_omega": (C.c_int, [_vp, _vp, _op, _vp]),
+}
+
 _lib = None
 _nuts = None
+_pg = None
 _dense = None
 _factor = None
 _predict = None
@@ -296,6 +310,16 @@ def bind_dense(L):
 def load_dense():
     """The library with the dense-metric NUTS entry points bound (the same liblogreg_hip.so as load())."""
     return bind_dense(load())
+
+
+def bind_pg(L):
+    """`L` (a loaded library handle) with the Polya-Gamma entry points bound; resolved once per handle."""
+    return _bind(L, PG_SYMBOLS, "_pg")
+
+
+def load_pg():
+    """The library with the Polya-Gamma entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_pg(load())
 
 
 def load():

@@ -79,7 +79,8 @@ def _sources():
                                                                         os.path.join(INCLUDE, "logreg_hip_loo.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_cov.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_adapt.h"),
-                                                                        os.path.join(INCLUDE, "logreg_hip_dense.h")]
+                                                                        os.path.join(INCLUDE, "logreg_hip_dense.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_pg.h")]
 
 
 def _dirs(alt: bool):

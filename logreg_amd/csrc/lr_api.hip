@@ -21,6 +21,7 @@
 #include "../../include/logreg_hip_cov.h"
 #include "../../include/logreg_hip_adapt.h"
 #include "../../include/logreg_hip_dense.h"
+#include "../../include/logreg_hip_pg.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -41,6 +42,7 @@
 #include "lr_kernels.h"
 #include "lr_nuts.h"
 #include "lr_nuts_dense.h"
+#include "lr_pg.h"
 #include "lr_dense.h"
 #include "lr_adapt.h"
 #include "lr_dense_adapt.h"
@@ -123,7 +125,7 @@ int staged(const HostBuf (&b)[N], Launch&& launch) {
     return LR_OK;
 }
 
-// The arrays of a run.  tally: accept counts (uint32 per chain) or NUTS counters, tally_item bytes per chain; launches add to it, so it
+// The arrays of a run.  tally: accept counts (uint32 per chain), NUTS counters or Polya-Gamma counters, tally_item bytes per chain; launches add to it, so it
 // is copied in as well as out.  lp_state: RWMH / MALA only.  depth_out: NUTS only.
 struct RunArrays {
     void* state;
@@ -307,6 +309,39 @@ int run_nuts(lr_model* m, int kind, double eps, int max_depth, const lr_run_opts
                        });
 }
 
+// ---- Polya-Gamma Gibbs (include/logreg_hip_pg.h; kernel: lr_pg.h).  omega_out: lr_pg_omega (the draws of one sweep, nothing else written)
+static_assert(sizeof(lr::PgCounters) == sizeof(lr_pg_counters) && LR_KIND_PG == lr::kKindPg && LR_PG_TAG == lr::TAG_PG &&
+              LR_PG_MAX_ROUNDS == lr::kPgMaxRounds && LR_PG_MAX_TRIALS == lr::kPgMaxTrials && LR_PG_MAX_TERMS == lr::kPgMaxTerms, "logreg_hip_pg.h and lr_pg.h");
+template <typename T, int P>
+int pg_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
+    auto ma = model_args<T, P>(m);
+    lr::PgArgs<T, P> pa{};
+    pa.state = static_cast<T*>(d.state);
+    pa.out = static_cast<T*>(d.out);
+    pa.counters = static_cast<lr::PgCounters*>(d.tally);
+    pa.omega_out = static_cast<T*>(omega_out);
+    pa.C = o->n_chains;
+    pa.chain_offset = o->chain_offset;
+    pa.iters = o->iters;
+    pa.thin = o->thin;
+    pa.iter_offset = o->iter_offset;
+    pa.seed = o->seed;
+    pa.p = m->p;
+    for (int j = 0; j < P; ++j) {
+        pa.b[j] = j < m->p ? m->pg_b[(size_t)j] : 0.0;
+        pa.ivar[j] = j < m->p ? m->inv_var[j] : 1.0;
+    }
+    pa.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_PG, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const int rc = m->table->launch_pg(&cfg, o->n_chains, &ma, &pa);
+    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "PG launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return LR_OK;
+}
+int pg_launch_any(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, pg_launch, m, pl, st, o, d, omega_out)
+    return bad_width(m);
+}
+
 // signed rows  xs_i = s_i x_i  of a design X [n][p], zero-padded to P columns, in the compute dtype;  s_i = 2 y_i - 1, or 1 without labels
 // (`sign`, where given, receives them).  `name` is the caller's word for X in the message.
 int signed_rows(const char* name, const double* X, const double* y, int64_t n, int p, int P, int dtype, std::vector<unsigned char>* host, signed char* sign) {
@@ -417,6 +452,11 @@ int lr_model_create(const double* X, const double* y, int64_t n, int32_t p, cons
     m->ysign.resize((size_t)n);
     if ((rc = signed_rows("X", X, y, n, p, P, dtype, &host, m->ysign.data()))) return rc;
     if ((rc = upload("lr_model_create", "rows", host.data(), host.size(), &m->d_rows, LR_ERR_HIP))) return rc;
+    m->pg_b.assign((size_t)p, 0.0);  // X^T (y - 1/2) of the stored rows, summed in row order (include/logreg_hip_pg.h)
+    for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < p; ++j)
+            m->pg_b[(size_t)j] += dtype == LR_F32 ? (double)reinterpret_cast<const float*>(host.data())[i * P + j] : reinterpret_cast<const double*>(host.data())[i * P + j];
+    for (int j = 0; j < p; ++j) m->pg_b[(size_t)j] *= 0.5;
     // the rows as float32, for the operand images (float64 models: rounded once, where an image is built from them)
     std::vector<float> rounded;
     if (dtype != LR_F32 && (images.tall_mx || images.wide1)) {
@@ -546,7 +586,7 @@ int lr_plan_run_info(const lr_model* m, int32_t kind, const lr_run_opts* o, lr_p
     if (!out) return fail(LR_ERR_INVALID, "out is NULL");
     int rc = check_opts(m, o, false);
     if (rc) return rc;
-    if (kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
+    if ((kind < LR_KIND_RWMH || kind > LR_KIND_NUTS) && kind != LR_KIND_PG) return fail(LR_ERR_INVALID, "kind must be one of LR_KIND_*");
     Plan pl;
     rc = plan_run(m, kind, o, LR_NUTS_MAX_DEPTH, &pl);
     if (rc) return rc;
@@ -664,6 +704,35 @@ int lr_run_nuts_dense(lr_model* m, void* state, double eps, int32_t max_depth, c
                         mt->who = "dense ";
                         return dense_factor_device(m, st, f, &mt->factor);
                     });
+}
+
+// Polya-Gamma Gibbs (include/logreg_hip_pg.h; the tuning-free counterpart of R/fit-rjags.R).  opts->precision is not read, lp_state does
+// not exist, the run is one part (plan_pg).
+int lr_run_pg(lr_model* m, void* state, const lr_run_opts* o, void* out, lr_pg_counters* counters) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    return run_request(m, LR_KIND_PG, 0, o, RunArrays{state, nullptr, out, counters, sizeof(lr_pg_counters), nullptr},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) { return pg_launch_any(m, pl, st, oo, d, nullptr); });
+}
+
+// the omega of one sweep at opts->iter_offset: the state is read, nothing but omega_out is written
+int lr_pg_omega(lr_model* m, const void* state, const lr_run_opts* o, void* omega_out) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    if (!o) return fail(LR_ERR_INVALID, "opts is NULL");
+    if (!omega_out) return fail(LR_ERR_INVALID, "omega_out is NULL");
+    lr_run_opts one = *o;  // (iters and thin are not read: one sweep)
+    one.iters = 1;
+    one.thin = 1;
+    one.stats = nullptr;
+    int rc = check_opts(m, &one, true);
+    if (rc) return rc;
+    if (!state) return fail(LR_ERR_INVALID, "state is NULL");
+    LR_HIP(hipSetDevice(m->device));
+    Plan pl;
+    if ((rc = plan_run(m, LR_KIND_PG, &one, 0, &pl))) return rc;
+    if (one.on_device) return pg_launch_any(m, pl, (hipStream_t)one.stream, &one, RunArrays{const_cast<void*>(state), nullptr, nullptr, nullptr, 0, nullptr}, omega_out);
+    const size_t C = (size_t)one.n_chains;
+    const HostBuf b[] = {{const_cast<void*>(state), C * m->p * m->esize(), true, false}, {omega_out, C * (size_t)m->n * m->esize(), false, true}};
+    return staged(b, [&](void* const* d) { return pg_launch_any(m, pl, nullptr, &one, RunArrays{d[0], nullptr, nullptr, nullptr, 0, nullptr}, d[1]); });
 }
 
 int lr_hessian(lr_model* m, const double* beta, double* lpost, double* grad, double* hess, void* stream) {

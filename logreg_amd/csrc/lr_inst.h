@@ -78,6 +78,9 @@ struct InstTable {
     // NUTS, rows in LDS on 16 lanes per chain; `nuts_args` is the argument struct of `variant` (a NutsVariant); cfg->lds_bytes = rows +
     // checkpoints, + the two matrices under a dense metric; null where the width has no NUTS kernel
     int (*launch_nuts)(const LaunchCfg*, int64_t C, const void* model_args, const void* nuts_args, int variant);
+    // the Polya-Gamma Gibbs sampler, rows in LDS on 16 lanes per chain (lr_pg.h); `pg_args` is a PgArgs<T, P>; cfg->lds_bytes = rows +
+    // the omega staging; null where the width has no such kernel
+    int (*launch_pg)(const LaunchCfg*, int64_t C, const void* model_args, const void* pg_args);
 };
 
 }  // namespace lr

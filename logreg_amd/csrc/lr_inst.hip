@@ -4,6 +4,7 @@
 #include "lr_kernels.h"
 #include "lr_nuts.h"
 #include "lr_nuts_dense.h"
+#include "lr_pg.h"
 #include "lr_tall.h"
 #if LR_DTYPE == 0 && LR_P >= 8
 #include "lr_mfma.h"
@@ -300,8 +301,15 @@ int launch_nuts(const LaunchCfg* cfg, int64_t C, const void* model_args, const v
     }
 }
 
+// Polya-Gamma Gibbs: one kernel per (dtype, padded p), rows in LDS, 16 lanes per chain (lr_pg.h); cfg->lds_bytes = rows + omega staging
+int launch_pg(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* pg_args) {
+    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
+    return launch_capped<&k_pg<T, P>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, *static_cast<const ModelArgs<T, P>*>(model_args),
+                                      *static_cast<const PgArgs<T, P>*>(pg_args));
+}
+
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg};
 
 }  // namespace
 }  // namespace lr

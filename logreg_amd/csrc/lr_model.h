@@ -166,6 +166,8 @@ struct lr_model {
     // `factor`), one per caller stream as the workspaces; `sigma` is the lower triangle it was made from
     struct DenseFactor { hipStream_t stream; void* p; std::vector<double> sigma; };
     std::vector<DenseFactor> dense;
+    // Polya-Gamma Gibbs (include/logreg_hip_pg.h): b = 1/2 sum_i xs_i = X^T (y - 1/2) of the rows as the model stores them, [p], float64
+    std::vector<double> pg_b;
     size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
 };
 

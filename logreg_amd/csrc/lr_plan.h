@@ -9,6 +9,7 @@
 // at shapes on both sides of the table's boundaries and fails when AUTO is more than 10 % off the best.
 #pragma once
 #include "../../include/logreg_hip_nuts.h"  // LR_KIND_NUTS (plan_run)
+#include "../../include/logreg_hip_pg.h"    // LR_KIND_PG
 
 namespace {
 
@@ -546,8 +547,29 @@ int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, 
     return LR_OK;
 }
 
+// Polya-Gamma Gibbs (include/logreg_hip_pg.h): one kernel family, rows in LDS on 16 lanes per chain (lr_pg.h), planned as ONE part.  The
+// LDS figure is the rows + the omega staging of a workgroup's 16 chains (the kernel keeps A and its factor in registers: no workspace).
+static_assert(LR_KIND_PG != kKindNutsDense && LR_KIND_PG > LR_KIND_NUTS, "LR_KIND_PG is a value of its own");
+size_t pg_lds_bytes(const lr_model* m) { return lds_rows_bytes(m) + (size_t)16 * (size_t)m->n * m->esize(); }
+int plan_pg(const lr_model* m, int group, int mode, Plan* out) {
+    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "PG: p = %d > 32 -- the Polya-Gamma kernel keeps a chain's p x p matrix on 16 lanes, up to p = 32", m->p);
+    if (m->n >= LR_PG_MAX_ROWS)
+        return fail(LR_ERR_UNSUPPORTED, "PG: n = %lld >= %d -- a row's random sub-stream is addressed by 16 bits of the block number", (long long)m->n, LR_PG_MAX_ROWS);
+    if (mode != LR_MODE_AUTO && mode != LR_MODE_LDS)
+        return fail(LR_ERR_UNSUPPORTED, "PG: mode %d has no Polya-Gamma kernel (rows in LDS only: LR_MODE_LDS or LR_MODE_AUTO)", mode);
+    if (group != 0 && group != 16) return fail(LR_ERR_UNSUPPORTED, "PG: group %d has no Polya-Gamma kernel (16 lanes per chain only)", group);
+    const size_t bytes = pg_lds_bytes(m);
+    if (bytes > kLdsBudget)
+        return fail(LR_ERR_UNSUPPORTED, "PG: the rows (n = %lld, %zu bytes) and the omega staging (%zu bytes) need %zu bytes of LDS, beyond the %zu a "
+                    "workgroup may use", (long long)m->n, lds_rows_bytes(m), bytes - lds_rows_bytes(m), bytes, kLdsBudget);
+    if (!m->table || !m->table->launch_pg) return fail(LR_ERR_UNSUPPORTED, "PG: no kernel for padded p = %d", m->P);
+    *out = Plan{lr::MODE_LDS, 16, 0, bytes};
+    return LR_OK;
+}
+
 // the plan of a run of `kind` (LR_KIND_*, or kKindNutsDense): every lr_run_*, lr_plan_run_info and tests/host/plan_harness.hip come through here
 int plan_run(const lr_model* m, int kind, const lr_run_opts* o, int max_depth, Plan* out) {
+    if (kind == LR_KIND_PG) return plan_pg(m, o->group, o->mode, out);
     if (kind == LR_KIND_NUTS || kind == kKindNutsDense) return plan_nuts(m, o->group, o->mode, max_depth, out, kind == kKindNutsDense);
     return make_plan(plan_request(m, kind, o), out);
 }

@@ -5,6 +5,7 @@
     hmcKernel(lpi, glpi, eps=1e-4, l=10, dmm=1)  fit-np-hmc.py:65-87
     ulKernel(glpi, dt=1e-4, pre=1)               fit-np-ul.py:61-68
     nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10)   blackjax.nuts in fit-blackjax-nuts.py:101 (dmm = 1 / pre)
+    pgKernel(lpost)                              the tuning-free Gibbs sampler (fit-rjags.R's role): Polya-Gamma augmentation
     mcmc(init, kernel, thin=10, iters=10000, verb=True)   fit-np-hmc.py:89-103
 
 When the callables passed in are the closures of a `LogReg` model (and, for RWMH, a
@@ -33,6 +34,9 @@ from .model import DeviceArray, LogReg, ModelFn
 # lr_nuts_counters (include/logreg_hip_nuts.h) as a NumPy record
 NUTS_COUNTERS = np.dtype([("n_leapfrog", "<u8"), ("depth_sum", "<u8"), ("accept_stat_sum", "<f8"), ("divergent", "<u4"),
                           ("max_depth_hits", "<u4")])
+# lr_pg_counters (include/logreg_hip_pg.h) as a NumPy record
+PG_COUNTERS = np.dtype([("proposals", "<u8"), ("series_terms", "<u8"), ("skipped", "<u4"), ("reserved", "<u4")])
+_COUNTERS_BY_KIND = {"nuts": ("nuts_", NUTS_COUNTERS), "pg": ("pg_", PG_COUNTERS)}  # checkpoint prefix, record
 
 
 # ------------------------------------------------------------------------------------------------
@@ -126,9 +130,9 @@ def _probe_random_walk(rprop, p):
 class FusedKernel:
     """A transition kernel whose whole step runs inside the HIP chain kernel.
 
-    kind in {"rwmh", "mala", "hmc", "ul", "nuts"}.  Calling it performs ONE iteration on the device with
+    kind in {"rwmh", "mala", "hmc", "ul", "nuts", "pg"}.  Calling it performs ONE iteration on the device with
     the reference's per-step signature: `kernel(x, ll) -> (x, ll)` for rwmh/mala (the threaded
-    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul/nuts.  Successive calls use
+    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul/nuts/pg.  Successive calls use
     successive iteration indices of the kernel's own Philox stream.
     """
 
@@ -148,10 +152,13 @@ class FusedKernel:
 
     def launch(self, opts: RunOpts, state_ptr, lp_ptr, out_ptr, acc_ptr, counters_ptr=None, depth_ptr=None):
         """One lr_run_<kind> call.  NUTS has no accept counts and no threaded log-density: it takes the per-chain counters
-        (lr_nuts_counters) and the optional tree depths of the kept rows instead."""
+        (lr_nuts_counters) and the optional tree depths of the kept rows instead; the Polya-Gamma sampler its own counters
+        (lr_pg_counters)."""
         L = self.model._L
         h = self.model.handle
-        if self.kind == "nuts" and self.params.get("inv_metric") is not None:  # dense metric (include/logreg_hip_dense.h)
+        if self.kind == "pg":
+            check(_lib.bind_pg(L).lr_run_pg(h, state_ptr, C.byref(opts), out_ptr, counters_ptr))
+        elif self.kind == "nuts" and self.params.get("inv_metric") is not None:  # dense metric (include/logreg_hip_dense.h)
             v = self.params["inv_metric"]
             check(_lib.bind_dense(L).lr_run_nuts_dense(h, state_ptr, float(self.params["eps"]), int(self.params["max_depth"]), v.ctypes.data,
                                                        C.byref(opts), out_ptr, counters_ptr, depth_ptr))
@@ -338,6 +345,19 @@ def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10, *, inv_metric=None):
     return _numpy_nuts(lpi, glpi, float(eps), dmm, max_depth)
 
 
+def pgKernel(lpost):
+    """The Polya-Gamma Gibbs sampler of Polson, Scott & Windle (2013) for the logistic-regression posterior of a `LogReg`: an exact
+    Gibbs sweep per iteration (omega_i ~ PG(1, |x_i . beta|), then beta ~ N(A^-1 b, A^-1)), with no tuning constant, no accept step
+    and no warm-up (include/logreg_hip_pg.h).  Takes the model's `lpost` closure and returns `FusedKernel("pg", model)`.
+
+    The sampler is built from the design X and the labels y, not from a log-density, so anything but a LogReg's closure is refused."""
+    model = _model_of(lpost, "lpost")
+    if model is None:
+        raise TypeError("pgKernel needs the `lpost` closure of a LogReg: the Polya-Gamma sampler is built from the model's X, y and prior "
+                        f"scale, not from a log-density it could call (got {type(lpost).__name__})")
+    return FusedKernel("pg", model)
+
+
 def _numpy_nuts(lpi, glpi, eps, dmm, max_depth, dense=None):
     """The same algorithm on NumPy arrays for arbitrary callables (the generic path: NumPy's global generator, no model arithmetic of
     its own).  `dense` = (Sigma, (s, R, A)): the dense metric -- `c` below is then the matrix Sigma, applied as a product."""
@@ -454,9 +474,9 @@ class ChainSet:
         self.lp = DeviceArray.from_host(m.device, lp0, dtype=np.float64)
         self.acc = DeviceArray(m.device, (self.C,), np.uint32)
         self.acc.zero_()
-        self.counters = None  # NUTS: per-chain lr_nuts_counters, added to by every launch
-        if kernel.kind == "nuts":
-            self.counters = DeviceArray(m.device, (self.C,), NUTS_COUNTERS)
+        self.counters = None  # NUTS / PG: per-chain lr_nuts_counters / lr_pg_counters, added to by every launch
+        if kernel.kind in _COUNTERS_BY_KIND:
+            self.counters = DeviceArray(m.device, (self.C,), _COUNTERS_BY_KIND[kernel.kind][1])
             self.counters.zero_()
         check(m._L.lr_stream_sync(m.device, None))
         # streaming statistics (enable_stats): device buffer [slots, C, 2, p], batch length, kept samples folded in
@@ -554,7 +574,7 @@ class ChainSet:
         """NUTS: the per-chain counters `[C]` (fields of lr_nuts_counters: n_leapfrog, depth_sum, accept_stat_sum, divergent,
         max_depth_hits), summed over every launch of this chain set."""
         if self.counters is None:
-            raise ValueError("counters exist for NUTS chain sets only")
+            raise ValueError("counters exist for NUTS and Polya-Gamma chain sets only")
         self.sync()
         return self.counters.to_host()
 
@@ -565,6 +585,17 @@ class ChainSet:
         return {"n_leapfrog": c["n_leapfrog"].astype(np.int64), "divergent": c["divergent"].astype(np.int64),
                 "max_depth_hits": c["max_depth_hits"].astype(np.int64), "mean_depth": c["depth_sum"] / n,
                 "mean_accept_stat": c["accept_stat_sum"] / n}
+
+    def pg_info(self) -> dict:
+        """Polya-Gamma: per-chain proposals, series_terms and skipped (lr_pg_counters) over the iterations run so far, and the two
+        ratios to rows x iterations (`proposals_per_draw`: theory <= 1.0009; skipped iterations draw nothing)."""
+        if self.kernel.kind != "pg":
+            raise ValueError("pg_info is for Polya-Gamma chain sets")
+        c = self.get_counters()
+        draws = np.maximum((self.iter_offset - c["skipped"].astype(np.int64)) * self.model.n, 1)
+        return {"proposals": c["proposals"].astype(np.int64), "series_terms": c["series_terms"].astype(np.int64),
+                "skipped": c["skipped"].astype(np.int64), "proposals_per_draw": c["proposals"] / draws,
+                "series_terms_per_draw": c["series_terms"] / draws}
 
     # -- checkpoint / resume (the reference has none: a run is all-or-nothing).  Because the random
     # stream is counter-based, (state, threaded ll, iteration counter, seed, chain offset) IS the
@@ -584,9 +615,10 @@ class ChainSet:
               "iter_offset": np.int64(self.iter_offset), "seed": np.uint64(self.seed),
               "chain_offset": np.int64(self.chain_offset), "plan_chains": np.int64(self.plan_chains),
               "plan_first": np.int64(self.plan_first), **self._fingerprint()}
-        if self.counters is not None:  # NUTS counters, field by field
+        if self.counters is not None:  # NUTS / PG counters, field by field
             cn = self.counters.to_host()
-            ck.update({"nuts_" + f: cn[f].copy() for f in NUTS_COUNTERS.names})
+            prefix, rec = _COUNTERS_BY_KIND[self.kernel.kind]
+            ck.update({prefix + f: cn[f].copy() for f in rec.names})
         if self.stats is not None:  # the statistics window travels with the run
             ck.update(stats=self.stats.to_host(), stats_batch=np.int64(self.stats_batch), stats_kept=np.int64(self.stats_kept),
                       stats_pivot=np.asarray(self.pivot, dtype=np.float64))
@@ -627,11 +659,13 @@ class ChainSet:
                                  f"{val!r} here (a resumed run would silently stop being the continuation)")
         cs.iter_offset = int(ckpt["iter_offset"])
         cs.acc.copy_from(np.asarray(ckpt["accepts"], dtype=np.uint32))
-        if cs.counters is not None and "nuts_n_leapfrog" in ckpt:
-            cn = np.zeros(cs.C, dtype=NUTS_COUNTERS)
-            for f in NUTS_COUNTERS.names:
-                cn[f] = ckpt["nuts_" + f]
-            cs.counters.copy_from(cn)
+        if cs.counters is not None:
+            prefix, rec = _COUNTERS_BY_KIND[kernel.kind]
+            if prefix + rec.names[0] in ckpt:
+                cn = np.zeros(cs.C, dtype=rec)
+                for f in rec.names:
+                    cn[f] = ckpt[prefix + f]
+                cs.counters.copy_from(cn)
         if "stats" in ckpt:
             st = np.asarray(ckpt["stats"], dtype=np.float64)
             cs.enable_stats(int(ckpt["stats_batch"]), st.shape[0], pivot=ckpt["stats_pivot"])
@@ -649,7 +683,8 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
     if kernel.kind == "nuts":
         evals = evals_per_iter if evals_per_iter else 2 ** int(kernel.params["max_depth"]) - 1
     else:
-        evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1}[kernel.kind]
+        # (a Polya-Gamma sweep: n draws and n p (p + 1) / 2 multiply-adds -- priced as p / 2 + 8 passes over the data)
+        evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1, "pg": kernel.model.p / 2 + 8}[kernel.kind]
     work_per_kept = max(1, int(thin * evals * kernel.model.n * kernel.model.p))
     return int(max(1, min(iters, 2_000_000_000 // work_per_kept)))
 
@@ -716,6 +751,9 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     chunk's block of kept samples is appended to its log-likelihood matrix on the device where `predictive` is fed; the summary dict --
     or, with `return_info=True`, the info dict -- gains `"loo": loo.result()` (elpd_loo, p_loo, se, looic, the Pareto k-hat per
     observation).  Chains, states, statistics and accept counts are those of the same call without it.
+    A `pgKernel` (the Polya-Gamma Gibbs sampler) has no accept count: `return_info=True` and `summary_only=True` report its per-chain
+    counters instead (`proposals`, `series_terms`, `skipped` and the two ratios of `ChainSet.pg_info`); `accept_rate` is the share of
+    sweeps that were not skipped.
     `plan_chains`, `plan_first`: chain count to plan the kernel variant for and the global id of that run's first chain (a shard of
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
@@ -789,6 +827,9 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         if nuts:  # the mean acceptance statistic in place of an acceptance rate
             ni = cs.nuts_info()
             res.update(ni, accept_rate=float(np.mean(ni["mean_accept_stat"])))
+        elif kernel.kind == "pg":  # a Gibbs sweep always moves, unless it was skipped
+            gi = cs.pg_info()
+            res.update(gi, accept_rate=float(1.0 - gi["skipped"].sum() / (cs.C * iters * thin)))
         else:
             res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)))
         res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
@@ -815,6 +856,8 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     if return_info:
         if nuts:  # per chain: n_leapfrog, divergent, max_depth_hits, mean_depth, mean_accept_stat
             info = {"state": cs.get_state(), "seed": seed, "plan": cs.plan(), "iterations": iters * thin, **cs.nuts_info()}
+        elif kernel.kind == "pg":  # per chain: proposals, series_terms, skipped and the two ratios
+            info = {"state": cs.get_state(), "seed": seed, "plan": cs.plan(), "iterations": iters * thin, **cs.pg_info()}
         else:
             info = {"accepts": cs.get_accepts(), "state": cs.get_state(), "ll": cs.get_ll(), "seed": seed,
                     "plan": cs.plan(), "iterations": iters * thin}
