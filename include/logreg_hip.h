@@ -180,6 +180,8 @@ LR_API int lr_model_interior_format(const lr_model* m, int32_t* format);
  * Replaces fit-np-hmc.py:23-24 (ll), :33-34 (lprior), :36-37 (lpost), :44-47 (glp).
  * beta [C,p]; ll/lprior/lpost [C]; grad [C,p]; any output may be NULL.
  * Only n_chains, group, mode, on_device, stream of `opts` are read.
+ * The values are those of exact-arithmetic log sigma(t_i), t_i = (2 y_i - 1) x_i . beta, however large |t_i| is: finite, and ll <= 0, where
+ * the reference's naive log(1 + exp(.)) overflows to -inf (t_i < -709); tests/eval_reference.py states the error bounds.
  */
 LR_API int lr_eval(lr_model* m, const void* beta, void* ll, void* lprior, void* lpost, void* grad,
                    const lr_run_opts* opts);

@@ -125,6 +125,10 @@ __global__ void __launch_bounds__(256) k_eval(ModelArgs<T, P> m, EvalArgs<T> a) 
     for (int j = 0; j < P; ++j) beta[j] = j < a.p ? a.beta[chain * a.p + j] : T(0);
     double ll, lpr;
     eval_lpost<T, P, G, true, true>(rows, m.prior, beta, grad, ll, lpr);
+    // ll is a sum of log sigma(.) <= 0, but where every row is saturated its computed value can come out a few ulp ABOVE zero: ts - log2(1 + 2^ts)
+    // cancels to +-ulp(ts) per row, and the padded rows' -log 2 against value_fixup() to ulp(their sum) -- separated, saturated states gave
+    // ll up to +2.5e-5 where the exact value is a tiny negative number.  What lr_eval returns is held to the sign (a NaN stays: the comparison is false for it).
+    if (ll > 0.0) ll = 0.0;
     if (live && gl == 0) {
         if (a.ll) a.ll[chain] = (T)ll;
         if (a.lprior) a.lprior[chain] = (T)lpr;
