@@ -16,8 +16,25 @@
  *   - there is no lp_state: the log-posterior at the current state is recomputed at the start of every call;
  *   - a run is always planned as ONE part (lr_plan_info.split = 0): the trees of a wave run in lockstep, and a second variant
  *     for the remainder of a chain count would not shorten the longest tree;
- *   - the kernel keeps the data rows in LDS (LR_MODE_LDS, 16 lanes per chain): shapes with no such variant -- p > 32, tall data
- *     that the stepwise engine would take, rows beyond the LDS -- return LR_ERR_UNSUPPORTED with the reason.
+ *   - the fused kernel keeps the data rows in LDS (LR_MODE_LDS, 16 lanes per chain): under LR_MODE_AUTO shapes with no such variant
+ *     -- p > 32, rows beyond the LDS -- return LR_ERR_UNSUPPORTED with the reason, which names the mode that takes them:
+ *   - opts->mode = LR_MODE_STEPWISE runs lr_run_nuts on the stepwise engine for exactly those shapes -- p > 32 (up to 128), or rows and
+ *     checkpoints at LR_NUTS_MAX_DEPTH beyond the LDS; a shape the fused kernel takes keeps refusing this mode, as it always did:
+ *     per leapfrog step one evaluation over all row slices and one update launch that does the tree bookkeeping (lr_tall_nuts.h).  All
+ *     chains of the call build their trees in lockstep, so every building chain is at the same leaf of the same doubling.  The plan
+ *     is the stepwise plan of the other samplers (lr_plan_info: mode stepwise, group = row slices, rows = slice length, one part;
+ *     opts->group pins the slice count and with it the order of the sums).  The same random stream: the same Markov chain as the
+ *     fused kernel up to the order of the sums.  What differs for the caller:
+ *       . the call is NOT a pure enqueue.  At the end of every doubling but the last possible one the host reads, on opts->stream, how
+ *         many chains are still building, and ends the iteration when none is: up to max_depth - 1 waits per iteration, each a
+ *         synchronisation of that stream.  All work stays on that stream; the loop is bounded by 2^max_depth - 1 steps whatever is
+ *         read, and the results do not depend on when the host looks (a finished chain applies nothing).  It cannot be captured
+ *         into a graph;
+ *       . workspace: behind the stepwise engine's own, (15 + 2 max_depth) x C x P elements of the model's type (P = p padded to 4, 8,
+ *         16, 32, 64 or 128) + 112 bytes per chain (224 at P = 128), kept per (model, stream) like the engine's; LR_ERR_NOMEM with the byte count;
+ *       . at most 65535 x 64 chains per call, as for every run on the stepwise engine;
+ *       . the diagonal metric only: lr_run_nuts_dense and the warm-up (logreg_hip_adapt.h) refuse LR_MODE_STEPWISE and p > 32.
+ *     LR_MODE_AUTO never chooses this path.
  *
  * Random stream (DESIGN.md "NUTS"): Philox4x32-10, key = seed, counter = (chain, iter_lo, iter_hi, block):
  *   momentum      normal blocks 0 .. ceil(p/4) - 1, as lr_run_hmc draws it

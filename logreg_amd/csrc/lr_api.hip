@@ -52,6 +52,7 @@
 #include "lr_loo.h"
 #include "lr_stats.h"
 #include "lr_tall.h"
+#include "lr_tall_nuts.h"
 #include "lr_tall_mx.h"
 #include "lr_wide_bf16.h"
 
@@ -231,6 +232,12 @@ int nuts_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* 
     return LR_OK;
 }
 int nuts_launch_any(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, double eps, int max_depth, const NutsMetric& mt, const RunArrays& d) {
+    if (pl.mode == lr::MODE_STEPWISE) {  // (planned for the diagonal metric of lr_run_nuts only: plan_run)
+        RunSpec rs{};
+        rs.kind = lr::KIND_HMC;
+        diag_tuning(m->p, eps, mt.dmm, &rs.step, rs.a, rs.b, rs.c);
+        return do_nuts_stepwise(m, pl, st, rs, o, max_depth, d.state, d.out, d.tally, d.depth_out);
+    }
     LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, nuts_launch, m, pl, st, o, eps, max_depth, mt, d)
     return bad_width(m);
 }

@@ -128,8 +128,9 @@ int do_chain_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, c
 }
 
 template <typename T, int P>
-int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t Cp, lr::TallArgs<T, P>* pa) {
+int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t Cp, lr::TallArgs<T, P>* pa, size_t extra = 0, unsigned char** extra_out = nullptr) {
     // C: chains of this call (sizes the workspace and the grids);  Cp: chains the slicing decisions are made for
+    // extra: bytes the caller carves itself, behind the engine's own pieces of the same block (NUTS: lr_nuts_sched.h)
     lr::TallArgs<T, P>& a = *pa;
     // every field starts from zero: the flags a run sets only on some paths (part_f32, fuse_mid, interior) were left to whatever the
     // caller's stack held -- found in round 5 when a float64 run on the trajectory kernels, which never touches part_f32, now and then
@@ -146,7 +147,7 @@ int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t C
     const size_t pg = align((size_t)RSmax * C * P * sizeof(T)), cv = align((size_t)2 * P * sizeof(T));
     // (second state pair + second partial buffer + constants: the fused interior steps of the row-split kernels)
     const size_t need = 4 * vec + 2 * dbl + align((size_t)C * 4) + pg + align((size_t)RS * C * sizeof(double)) +
-                        (RS_i > 0 && (m->P > 32 || rs_waves == 16) ? 2 * vec + pg : 0) + cv;
+                        (RS_i > 0 && (m->P > 32 || rs_waves == 16) ? 2 * vec + pg : 0) + cv + extra;
     lr_model::Ws* slot = nullptr;
     for (auto& e : m->ws)
         if (e.stream == st) slot = &e;
@@ -199,6 +200,7 @@ int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t C
         a.pm_in = (const T*)carve(vec);
         a.part_in = (const T*)carve(pg);
     }
+    if (extra_out) *extra_out = carve(extra);
     a.C = C;
     a.p = m->p;
     {
@@ -381,6 +383,67 @@ int do_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs
     return LR_OK;
 }
 
+// NUTS on the stepwise engine (lr_tall_nuts.h; the schedule: lr_nuts_sched.h).  Per iteration: for every leaf the evaluation at q1 and
+// the leaf's update launch.  The one thing the host learns from the device is how many chains are still building, read at the end of
+// a doubling on the caller's stream (at most max_depth - 1 waits per iteration); zero ends the iteration.  The loop is bounded by
+// 2^max_depth - 1 leaves whatever it reads, and a finished chain is inert, so the results do not depend on when the host looks.
+template <typename T, int P>
+int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, int max_depth, void* state, void* out,
+                       void* counters, int8_t* depth_out) {
+    const int64_t C = o->n_chains, Cp = plan_count(o);
+    if ((C + 63) / 64 > 65535) return fail(LR_ERR_UNSUPPORTED, "the stepwise engine takes at most %lld chains per call (got %lld): split the run into shards (chain_offset)", 65535LL * 64, (long long)C);
+    const lr::InstTable* t = m->table;
+    if (!t->launch_tall_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
+    const lr::NutsTallCarve cv = lr::nuts_tall_carve(C, P, sizeof(T), max_depth);
+    lr::TallArgs<T, P> a;
+    unsigned char* w = nullptr;
+    int rc = setup_tall<T, P>(m, pl, st, C, Cp, &a, cv.total, &w);
+    if (rc) return rc;
+    a.RS_i = 0;  // full precision at every leaf: no reduced-precision interior, no trajectory kernel
+    a.state = static_cast<T*>(state);
+    a.out = static_cast<T*>(out);
+    a.chain_offset = o->chain_offset;
+    a.seed = o->seed;
+    a.step = (T)rs.step;
+    for (int j = 0; j < P; ++j) {
+        a.a[j] = (T)rs.a[j];
+        a.b[j] = (T)rs.b[j];
+        a.c[j] = (T)rs.c[j];
+    }
+    a.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    const lr::NutsTallArgs<T> na{reinterpret_cast<T*>(w + cv.vec_off), reinterpret_cast<lr::NutsTallChain*>(w + cv.chain_off), reinterpret_cast<uint32_t*>(w + cv.tally_off),
+                                 static_cast<lr::NutsCounters*>(counters), depth_out, max_depth};
+    auto K = [&]() {
+        if (!rc) rc = t->launch_tall_partial(st, 1, 1, &a);
+    };
+    auto N = [&](int phase, int64_t iter, const lr::NutsStep& leaf, int64_t out_row, int flag) {
+        if (!rc) rc = t->launch_tall_nuts(st, &a, &na, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag);
+    };
+    const lr::NutsStep none{};
+    if (!rc) rc = t->launch_tall_update(st, lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0, &a);
+    K();
+    N(lr::NPH_BEGIN, o->iter_offset, none, -1, 1);
+    const int64_t total = o->iters * o->thin;
+    for (int64_t tt = 0; tt < total && !rc; ++tt) {
+        for (lr::NutsSched sch(max_depth); !sch.done() && !rc;) {
+            const lr::NutsStep leaf = sch.cur();
+            K();
+            N(lr::NPH_LEAF, o->iter_offset + tt, leaf, -1, leaf.read);
+            uint32_t building = 1;
+            if (leaf.read && !rc) {
+                if (hipMemcpyAsync(&building, na.tally + leaf.d, sizeof(building), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+                    return fail(LR_ERR_HIP, "NUTS: reading the tally of building chains failed: %s", hipGetErrorString(hipGetLastError()));
+            }
+            sch.advance(building);
+        }
+        const int64_t out_row = ((tt + 1) % o->thin == 0) ? (tt + 1) / o->thin - 1 : -1;
+        N(lr::NPH_END, o->iter_offset + tt, none, out_row, tt + 1 < total);
+    }
+    N(lr::NPH_STORE, 0, none, -1, 0);
+    if (rc) return fail(LR_ERR_HIP, "stepwise NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return LR_OK;
+}
+
 int bad_width(const lr_model* m) { return fail(LR_ERR_UNSUPPORTED, "unsupported padded width %d", m->P); }
 
 int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
@@ -402,6 +465,12 @@ int do_stepwise(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, 
 int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
                      void* lpost, void* grad) {
     LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_eval_stepwise_t, m, pl, st, C, beta, ll, lprior, lpost, grad)
+    return bad_width(m);
+}
+
+int do_nuts_stepwise(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, int max_depth, void* state, void* out, void* counters,
+                     int8_t* depth_out) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_nuts_stepwise_t, m, pl, st, rs, o, max_depth, state, out, counters, depth_out)
     return bad_width(m);
 }
 

@@ -81,6 +81,9 @@ struct InstTable {
     // the Polya-Gamma Gibbs sampler, rows in LDS on 16 lanes per chain (lr_pg.h); `pg_args` is a PgArgs<T, P>; cfg->lds_bytes = rows +
     // the omega staging; null where the width has no such kernel
     int (*launch_pg)(const LaunchCfg*, int64_t C, const void* model_args, const void* pg_args);
+    // NUTS on the stepwise engine (lr_tall_nuts.h): one update launch of k_tall_nuts_update; `tall_args` is a TallArgs<T,P>, `nuts_args` a
+    // NutsTallArgs<T>, `phase` a NutsTallPhase, (s, d, i) the leaf of lr_nuts_sched.h; every width of the stepwise engine has it
+    int (*launch_tall_nuts)(hipStream_t, const void* tall_args, const void* nuts_args, int phase, int64_t iter, int s, int d, int i, int64_t out_row, int flag);
 };
 
 }  // namespace lr

@@ -6,6 +6,7 @@
 #include "lr_nuts_dense.h"
 #include "lr_pg.h"
 #include "lr_tall.h"
+#include "lr_tall_nuts.h"
 #if LR_DTYPE == 0 && LR_P >= 8
 #include "lr_mfma.h"
 #endif
@@ -309,7 +310,7 @@ int launch_pg(const LaunchCfg* cfg, int64_t C, const void* model_args, const voi
 }
 
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg, &launch_tall_nuts_t<T, P>};
 
 }  // namespace
 }  // namespace lr

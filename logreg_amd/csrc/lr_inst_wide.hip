@@ -4,6 +4,7 @@
 // Compiled four times:  hipcc -DLR_P=64|128 -DLR_DTYPE=0|1 -DLR_SFX=f32_p64 ...
 #include "lr_inst.h"
 #include "lr_wide_bf16.h"
+#include "lr_tall_nuts.h"
 #if LR_DTYPE == 1
 #include "lr_wide_f64.h"
 #endif
@@ -105,7 +106,7 @@ int launch_tall_update(hipStream_t st, int kind, int phase, int64_t iter, int64_
     return check(hipGetLastError());
 }
 
-const InstTable kTable = {LR_DTYPE, P, 0, nullptr, nullptr, nullptr, &launch_tall_partial, &launch_tall_update, &launch_tall_traj, nullptr, nullptr, nullptr};
+const InstTable kTable = {LR_DTYPE, P, 0, nullptr, nullptr, nullptr, &launch_tall_partial, &launch_tall_update, &launch_tall_traj, nullptr, nullptr, nullptr, nullptr, &launch_tall_nuts_t<T, P>};
 
 }  // namespace
 }  // namespace lr

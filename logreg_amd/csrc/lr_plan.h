@@ -519,31 +519,52 @@ int make_plan(const PlanReq& q, Plan* out) {
     return LR_OK;
 }
 
-// NUTS (include/logreg_hip_nuts.h): one kernel family, rows in LDS on 16 lanes per chain (lr_nuts.h), planned as ONE part.  Everything
+// NUTS (include/logreg_hip_nuts.h): the fused kernel family, rows in LDS on 16 lanes per chain (lr_nuts.h), planned as ONE part.  Everything
 // else is refused with the reason: wide models, a forced mode or lane count the family does not have, rows and checkpoints beyond the
-// LDS (tall data: the stepwise engine has no NUTS kernel).  The LDS figure is the rows + the U-turn checkpoints at `max_depth`.
+// LDS.  The LDS figure is the rows + the U-turn checkpoints at `max_depth`.  Under the diagonal metric the caller may ask for the
+// stepwise engine instead (LR_MODE_STEPWISE: plan_nuts_stepwise below, reached from plan_run; the refusals of LR_MODE_AUTO say so);
+// under a dense metric, and for the warm-up, the stepwise (tall-data) engine has no NUTS kernel.
 size_t nuts_lds_bytes(const lr_model* m, int max_depth) {
     return lds_rows_bytes(m) + (size_t)2 * max_depth * ((m->P + 15) / 16) * 256 * m->esize();
 }
 // ... and under a dense metric (include/logreg_hip_dense.h) the two P x P matrices of lr_nuts_dense.h behind them
 constexpr int kKindNutsDense = LR_KIND_NUTS + 1;  // plan_run only: not a kind of the ABI
 size_t nuts_dense_lds_bytes(const lr_model* m) { return (size_t)2 * m->P * m->P * m->esize(); }
-int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, bool dense = false) {
-    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
-    if (mode == LR_MODE_STEPWISE) return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine has no NUTS kernel; NUTS runs with the rows in LDS");
+// (stepwise_hint: the caller is lr_run_nuts / lr_plan_run, which have the stepwise path to point at; the warm-up has none)
+int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, bool dense = false, bool stepwise_hint = false) {
+    const char* hint = dense || !stepwise_hint ? "" : "; lr_run_nuts takes it on the stepwise engine with mode = LR_MODE_STEPWISE (mode=\"stepwise\")";
+    if (m->P > 32 && dense) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel for a dense metric", m->p);
+    if (m->P > 32) return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models have no fused NUTS kernel%s", m->p, hint);
+    if (mode == LR_MODE_STEPWISE)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine has no NUTS kernel for a dense metric or the warm-up; there NUTS runs with the rows in LDS");
     if (mode != LR_MODE_AUTO && mode != LR_MODE_LDS)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: mode %d has no NUTS kernel (rows in LDS only: LR_MODE_LDS or LR_MODE_AUTO)", mode);
     if (group != 0 && group != 16) return fail(LR_ERR_UNSUPPORTED, "NUTS: group %d has no NUTS kernel (16 lanes per chain only)", group);
     const size_t bytes = nuts_lds_bytes(m, max_depth) + (dense ? nuts_dense_lds_bytes(m) : 0);
     if (bytes > kLdsBudget && dense)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes), the U-turn checkpoints and the dense metric's two matrices (%zu bytes) need %zu bytes "
-                    "of LDS, beyond the %zu a workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n,
+                    "of LDS, beyond the %zu a workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel for a dense metric", (long long)m->n,
                     lds_rows_bytes(m), nuts_dense_lds_bytes(m), bytes, kLdsBudget);
     if (bytes > kLdsBudget)
         return fail(LR_ERR_UNSUPPORTED, "NUTS: the rows (n = %lld, %zu bytes) and the U-turn checkpoints need %zu bytes of LDS, beyond the %zu a "
-                    "workgroup may use -- tall data runs on the stepwise engine, which has no NUTS kernel", (long long)m->n, lds_rows_bytes(m), bytes, kLdsBudget);
+                    "workgroup may use%s", (long long)m->n, lds_rows_bytes(m), bytes, kLdsBudget, hint);
     if (!m->table || !m->table->launch_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no kernel for padded p = %d", m->P);
     *out = Plan{lr::MODE_LDS, 16, 0, bytes};
+    return LR_OK;
+}
+
+// NUTS on the stepwise engine (lr_tall_nuts.h), at the caller's request (LR_MODE_STEPWISE), for the shapes the fused kernel has no variant
+// for -- p > 32, or rows and checkpoints (at LR_NUTS_MAX_DEPTH, whatever the call's max_depth: one rule for lr_plan_run and the run) beyond
+// the LDS: the stepwise plan of plan_wide / plan_tall -- group = row slices, rows_per_lane = slice length, one part.  A shape the fused
+// kernel takes keeps its refusal of this mode: nothing that ran, or was refused, before this path existed behaves differently.
+int plan_nuts_stepwise(const lr_model* m, const lr_run_opts* o, Plan* out) {
+    if (m->P <= 32 && nuts_lds_bytes(m, LR_NUTS_MAX_DEPTH) <= kLdsBudget)
+        return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine takes NUTS only where the fused kernel cannot (p > 32, or rows beyond the LDS); "
+                    "here (n = %lld, p = %d) NUTS runs with the rows in LDS", (long long)m->n, m->p);
+    if (!m->table || !m->table->launch_tall_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
+    const PlanReq q{m, plan_count(o), o->group, LR_MODE_STEPWISE, false, LR_KIND_NUTS, false, false};
+    if (m->P > 32) return plan_wide(q, out);
+    plan_tall(q, out);
     return LR_OK;
 }
 
@@ -570,7 +591,8 @@ int plan_pg(const lr_model* m, int group, int mode, Plan* out) {
 // the plan of a run of `kind` (LR_KIND_*, or kKindNutsDense): every lr_run_*, lr_plan_run_info and tests/host/plan_harness.hip come through here
 int plan_run(const lr_model* m, int kind, const lr_run_opts* o, int max_depth, Plan* out) {
     if (kind == LR_KIND_PG) return plan_pg(m, o->group, o->mode, out);
-    if (kind == LR_KIND_NUTS || kind == kKindNutsDense) return plan_nuts(m, o->group, o->mode, max_depth, out, kind == kKindNutsDense);
+    if (kind == LR_KIND_NUTS && o->mode == LR_MODE_STEPWISE) return plan_nuts_stepwise(m, o, out);
+    if (kind == LR_KIND_NUTS || kind == kKindNutsDense) return plan_nuts(m, o->group, o->mode, max_depth, out, kind == kKindNutsDense, true);
     return make_plan(plan_request(m, kind, o), out);
 }
 

@@ -250,6 +250,52 @@ __global__ void __launch_bounds__((64 * TallGeom<T, P>::NW)) k_tall_partial(Tall
     }
 }
 
+// The three pieces every update kernel of the engine is made of (k_tall_update below, k_tall_nuts_update of lr_tall_nuts.h), for
+// coordinate j of `chain` (ivj: the prior precision of j).  tall_reduced_value sums over the chain's lanes: all threads of the block call it.
+template <typename T, int P> __device__ __forceinline__ T tall_reduced_grad(const TallArgs<T, P>& a, int64_t chain, int j, T ivj) {  // likelihood partials in slice order + prior
+    // slice order, 16 loads in flight (a plain loop issues them one L2 round trip at a time: this kernel is
+    // nothing but that latency)
+    auto slices = [&](auto* pg) {
+        using E = std::remove_cv_t<std::remove_pointer_t<decltype(pg)>>;
+        double s = 0.0;
+        const int64_t stride = a.C * P;
+        int r = 0;
+        for (; r + 16 <= a.RS; r += 16) {
+            E t[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) t[u] = pg[(r + u) * stride];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) s += (double)t[u];
+        }
+        for (; r + 4 <= a.RS; r += 4) {
+            E t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = pg[(r + u) * stride];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s += (double)t[u];
+        }
+        for (; r < a.RS; ++r) s += (double)pg[r * stride];
+        return s;
+    };
+    // (float64 models after a reduced-precision interior kernel: that kernel's partials are float32 values, written as such)
+    const double s = sizeof(T) == 8 && a.part_f32 ? slices(reinterpret_cast<const float*>(a.part_g) + chain * P + j) : slices(a.part_g + chain * P + j);
+    return (T)s - a.q1[chain * P + j] * ivj;
+}
+template <typename T, int P> __device__ __forceinline__ double tall_reduced_value(const TallArgs<T, P>& a, int64_t chain, int j, T ivj) {  // lpost(q1) = sum of slice values + lprior(q1)
+    double s = 0.0;
+    for (int r = 0; r < a.RS; ++r) s += a.part_v[(int64_t)r * a.C + chain];
+    const T q = a.q1[chain * P + j];
+    const T quad = chain_sum<P>(q * q * ivj);
+    return s + a.prior.lprior_const - 0.5 * (double)quad;
+}
+template <typename T> __device__ __forceinline__ T tall_normal_j(uint64_t seed, uint64_t gchain, uint64_t it, int j) {  // coordinate j: Philox block j/4, word pair (j%4)/2, element j&1
+    const U4 w = philox4x32_10((uint32_t)gchain, (uint32_t)it, (uint32_t)(it >> 32), (uint32_t)(j >> 2), (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t wa = (j & 2) ? w.z : w.x, wb = (j & 2) ? w.w : w.y;
+    T z0, z1;
+    box_muller(wa, wb, z0, z1);
+    return (j & 1) ? z1 : z0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // one coordinate per lane; chain = (global thread) / P
 template <typename T, int P, int KIND>
@@ -264,50 +310,9 @@ __global__ void __launch_bounds__(256) k_tall_update(TallArgs<T, P> a, int phase
     const uint64_t gchain = (uint64_t)(a.chain_offset + chain);
     const T aj = a.a[j], bj = a.b[j], cj = a.c[j], ivj = a.prior.inv_var[j];
 
-    auto reduced_grad = [&]() {  // likelihood partials in slice order + prior
-        // slice order, 16 loads in flight (a plain loop issues them one L2 round trip at a time: this kernel is
-        // nothing but that latency)
-        auto slices = [&](auto* pg) {
-            using E = std::remove_cv_t<std::remove_pointer_t<decltype(pg)>>;
-            double s = 0.0;
-            const int64_t stride = a.C * P;
-            int r = 0;
-            for (; r + 16 <= a.RS; r += 16) {
-                E t[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) t[u] = pg[(r + u) * stride];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) s += (double)t[u];
-            }
-            for (; r + 4 <= a.RS; r += 4) {
-                E t[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[u] = pg[(r + u) * stride];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) s += (double)t[u];
-            }
-            for (; r < a.RS; ++r) s += (double)pg[r * stride];
-            return s;
-        };
-        // (float64 models after a reduced-precision interior kernel: that kernel's partials are float32 values, written as such)
-        const double s = sizeof(T) == 8 && a.part_f32 ? slices(reinterpret_cast<const float*>(a.part_g) + chain * P + j) : slices(a.part_g + chain * P + j);
-        return (T)s - a.q1[ix] * ivj;
-    };
-    auto reduced_value = [&]() {  // lpost(q1) = sum of slice values + lprior(q1)
-        double s = 0.0;
-        for (int r = 0; r < a.RS; ++r) s += a.part_v[(int64_t)r * a.C + chain];
-        const T q = a.q1[ix];
-        const T quad = chain_sum<P>(q * q * ivj);
-        return s + a.prior.lprior_const - 0.5 * (double)quad;
-    };
-    auto normal_j = [&](uint64_t it) {  // coordinate j: Philox block j/4, word pair (j%4)/2, element j&1
-        const U4 w = philox4x32_10((uint32_t)gchain, (uint32_t)it, (uint32_t)(it >> 32), (uint32_t)(j >> 2),
-                                   (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-        const uint32_t wa = (j & 2) ? w.z : w.x, wb = (j & 2) ? w.w : w.y;
-        T z0, z1;
-        box_muller(wa, wb, z0, z1);
-        return (j & 1) ? z1 : z0;
-    };
+    auto reduced_grad = [&]() { return tall_reduced_grad<T, P>(a, chain, j, ivj); };
+    auto reduced_value = [&]() { return tall_reduced_value<T, P>(a, chain, j, ivj); };
+    auto normal_j = [&](uint64_t it) { return tall_normal_j<T>(a.seed, gchain, it, j); };
     // start iteration `it` from (x, g, lp): draw, set q1 (+pm, aux)
     auto begin = [&](uint64_t it, T x, T g) {
         const T z = normal_j(it);

@@ -328,7 +328,12 @@ def nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10, *, inv_metric=None):
     q += eps * inv_metric p (include/logreg_hip_dense.h).  `dmm` is the diagonal case inv_metric = diag(1 / dmm).
 
     A LogReg's closures give a FusedKernel (include/logreg_hip_nuts.h); any other callables a plain NumPy NUTS that draws from
-    NumPy's global generator, like the other generic kernels."""
+    NumPy's global generator, like the other generic kernels.
+
+    The fused kernel keeps the rows in LDS: p <= 32 and a few thousand rows; beyond that the default mode raises with the reason.  Tall
+    and wide models (p <= 128) -- those shapes and no others -- run the same chain with `mcmc(..., mode="stepwise")` /
+    `ChainSet(..., mode="stepwise")`, diagonal metric only: one evaluation and one update launch per leapfrog step, all chains of a call in lockstep, `group=` the number of row slices
+    (`examples/fit_nuts_tall.py`).  Such a call waits on its stream up to `max_depth - 1` times per iteration."""
     max_depth = int(max_depth)
     if not 1 <= max_depth <= _lib.NUTS_MAX_DEPTH:
         raise ValueError(f"max_depth must be in 1..{_lib.NUTS_MAX_DEPTH}, got {max_depth}")
