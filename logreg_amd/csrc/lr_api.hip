@@ -560,7 +560,7 @@ int lr_model_debug_opts(const lr_model* m, char* buf, int len) {
 
 int lr_model_interior_format(const lr_model* m, int32_t* format) {
     if (!m || !format) return fail(LR_ERR_INVALID, "NULL argument");
-    if (m->P > 32) *format = (m->d_xblk1h && m->dbg.wide_f16 != 0) ? LR_INTERIOR_F16 : (m->d_xblk1 ? LR_INTERIOR_BF16 : LR_INTERIOR_NONE);
+    if (m->P > 32) *format = interior_f16(m) ? LR_INTERIOR_F16 : (m->d_xblk1 ? LR_INTERIOR_BF16 : LR_INTERIOR_NONE);
     else *format = m->P >= 8 ? LR_INTERIOR_BF16 : LR_INTERIOR_NONE;  // (the matrix-core kernels of lr_mfma.h / lr_mfma_f64.h / lr_tall_mx.h)
     return LR_OK;
 }

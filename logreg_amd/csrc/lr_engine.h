@@ -1,7 +1,8 @@
 // lr_engine.h -- the host side between the C ABI (lr_api.hip) and the kernel launches: packs the by-value kernel argument structs
-// from a model handle, a plan (lr_plan.h) and the caller's options, owns the stepwise engine's workspace and drives its launches
-// (load -> partial -> update per evaluation; the interior leapfrog steps on the reduced-precision kernels where the policy allows).
-// No arithmetic of the path happens here.  Included once, by lr_api.hip (after lr_model.h and lr_plan.h).
+// from a model handle, a plan (lr_plan.h) and the caller's options, owns the stepwise engine's workspace and states its launches
+// (load -> partial -> update per evaluation; the interior leapfrog steps as the StepwisePlan of lr_plan.h says: which kernel runs, on
+// which slicing, is decided there).  No arithmetic of the path and no choice of a kernel happens here.  Included once, by lr_api.hip
+// (after lr_model.h and lr_plan.h).
 #pragma once
 
 namespace {
@@ -24,6 +25,12 @@ struct RunSpec {
     int l;
     double a[kMaxP], b[kMaxP], c[kMaxP];
 };
+
+// step and per-coordinate vectors of a run in the kernels' type (ChainArgs, TallArgs)
+template <typename T, int P, typename Args> void fill_tuning(const RunSpec& rs, Args* a) {
+    a->step = (T)rs.step;
+    for (int j = 0; j < P; ++j) a->a[j] = (T)rs.a[j], a->b[j] = (T)rs.b[j], a->c[j] = (T)rs.c[j];
+}
 
 template <typename T, int P>
 int do_eval_t(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
@@ -61,11 +68,8 @@ int do_chain_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, c
     ca.seed = o->seed;
     ca.p = m->p;
     ca.l = rs.l;
-    ca.step = (T)rs.step;
+    fill_tuning<T, P>(rs, &ca);
     for (int j = 0; j < P; ++j) {
-        ca.a[j] = (T)rs.a[j];
-        ca.b[j] = (T)rs.b[j];
-        ca.c[j] = (T)rs.c[j];
         const double ks = sizeof(T) == 4 ? 1.4426950408889634 : 1.0;  // lr::ExpScale<T>::k
         ca.d[j] = (T)(rs.b[j] * ks);
         ca.e[j] = (T)(m->inv_var[j] / ks);
@@ -127,27 +131,25 @@ int do_chain_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, c
     return LR_OK;
 }
 
+// ---- the stepwise engine.  A run's argument block is filled ONCE -- setup_tall: model, StepwisePlan (lr_plan.h), workspace; then the
+// caller's arrays -- and is const from then on.  Every launch goes through TallRun::issue, which copies the block, applies what THAT
+// launch differs in (TallOver) and calls the table: no field is ever set for a launch and put back after it.
 template <typename T, int P>
-int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t Cp, lr::TallArgs<T, P>* pa, size_t extra = 0, unsigned char** extra_out = nullptr) {
-    // C: chains of this call (sizes the workspace and the grids);  Cp: chains the slicing decisions are made for
+int setup_tall(lr_model* m, const StepwisePlan& sp, hipStream_t st, int64_t C, lr::TallArgs<T, P>* pa, size_t extra = 0, unsigned char** extra_out = nullptr) {
+    // C: chains of this call (sizes the workspace and the grids; the plan was made for the run's: plan_count)
     // extra: bytes the caller carves itself, behind the engine's own pieces of the same block (NUTS: lr_nuts_sched.h)
-    lr::TallArgs<T, P>& a = *pa;
-    // every field starts from zero: the flags a run sets only on some paths (part_f32, fuse_mid, interior) were left to whatever the
+    // (chain blocks of 16 .. 128 chains are the grid's y / x dimension of the partial kernels: y is a 16-bit quantity)
+    if ((C + 63) / 64 > 65535) return fail(LR_ERR_UNSUPPORTED, "the stepwise engine takes at most %lld chains per call (got %lld): split the run into shards (chain_offset)", 65535LL * 64, (long long)C);
+    // every field starts from zero: the flags only some launches set (part_f32, fuse_mid, interior) were once left to whatever the
     // caller's stack held -- found in round 5 when a float64 run on the trajectory kernels, which never touches part_f32, now and then
     // had its end-point update read float64 partials as float32
-    a = lr::TallArgs<T, P>{};
-    const int RS = pl.G;
+    lr::TallArgs<T, P>& a = *pa = lr::TallArgs<T, P>{};
     auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t vec = align((size_t)C * P * sizeof(T)), dbl = align((size_t)C * sizeof(double));
-    // row slices of the reduced-precision interior leapfrog steps (lr_plan.h)
-    const InteriorPlan ip = plan_interior(m, Cp);
-    const int RS_i = ip.RS_i, rs_waves = ip.waves;
-    const int64_t slice_len_i = ip.slice_len_i;
-    const int RSmax = RS_i > RS ? RS_i : RS;
+    const int RSmax = sp.RS_i > sp.RS ? sp.RS_i : sp.RS;
     const size_t pg = align((size_t)RSmax * C * P * sizeof(T)), cv = align((size_t)2 * P * sizeof(T));
-    // (second state pair + second partial buffer + constants: the fused interior steps of the row-split kernels)
-    const size_t need = 4 * vec + 2 * dbl + align((size_t)C * 4) + pg + align((size_t)RS * C * sizeof(double)) +
-                        (RS_i > 0 && (m->P > 32 || rs_waves == 16) ? 2 * vec + pg : 0) + cv + extra;
+    // (second state pair + second partial buffer: the fused interior steps of the row-split kernels; constants)
+    const size_t need = 4 * vec + 2 * dbl + align((size_t)C * 4) + pg + align((size_t)sp.RS * C * sizeof(double)) + (sp.alt_buffers ? 2 * vec + pg : 0) + cv + extra;
     lr_model::Ws* slot = nullptr;
     for (auto& e : m->ws)
         if (e.stream == st) slot = &e;
@@ -162,224 +164,159 @@ int setup_tall(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, int64_t C
         slot = &m->ws.back();
     }
     if (need > slot->bytes) {
-        if (slot->p) {
-            // work already enqueued on this stream may still use the old block: hipFree waits for the device
-            (void)hipFree(slot->p);
-        }
-        slot->p = nullptr;
-        slot->bytes = 0;
+        if (slot->p) (void)hipFree(slot->p);  // (work already enqueued on this stream may still use the old block: hipFree waits for the device)
+        slot->p = nullptr, slot->bytes = 0;
         if (hipMalloc(&slot->p, need) != hipSuccess) return fail(LR_ERR_NOMEM, "stepwise workspace of %zu bytes", need);
         slot->bytes = need;
     }
     unsigned char* w = static_cast<unsigned char*>(slot->p);
     auto carve = [&](size_t b) { unsigned char* r = w; w += b; return r; };
-    std::memset(&a, 0, sizeof(a));
     a.rows = static_cast<const T*>(m->d_rows);
     a.rows_tw = static_cast<const float*>(m->d_rows_tw);
-    a.n = m->n;
-    a.slice_len = pl.R;
-    a.RS = RS;
+    a.n = m->n, a.C = C, a.p = m->p;
+    a.slice_len = sp.slice_len, a.RS = sp.RS;
     for (int j = 0; j < P; ++j) a.prior.inv_var[j] = (T)m->inv_var[j];
     a.prior.lprior_const = m->lprior_const;
-    a.x = (T*)carve(vec);
-    a.g = (T*)carve(vec);
-    a.q1 = (T*)carve(vec);
-    a.pm = (T*)carve(vec);
-    a.lp = (double*)carve(dbl);
-    a.aux = (double*)carve(dbl);
+    a.x = (T*)carve(vec), a.g = (T*)carve(vec);
+    a.q1 = (T*)carve(vec), a.pm = (T*)carve(vec);
+    a.lp = (double*)carve(dbl), a.aux = (double*)carve(dbl);
     a.nacc = (uint32_t*)carve(align((size_t)C * 4));
     a.part_g = (T*)carve(pg);
-    a.RS_i = RS_i;
-    a.traj_tiles = 1, a.traj_fmt = 0;  // (set per run by do_stepwise_t)
-    a.slice_len_i = slice_len_i;
-    a.rowsplit_waves = rs_waves;
-    a.part_v = (double*)carve(align((size_t)RS * C * sizeof(double)));
+    a.RS_i = sp.bf16_interior ? sp.RS_i : 0;
+    a.traj_tiles = sp.traj_tiles, a.traj_fmt = sp.traj_fmt;
+    a.slice_len_i = sp.slice_len_i, a.rowsplit_waves = sp.waves;
+    a.part_v = (double*)carve(align((size_t)sp.RS * C * sizeof(double)));
     a.cvec = (const T*)carve(cv);
-    if (RS_i > 0 && (m->P > 32 || rs_waves == 16)) {  // alternates, parked in the *_in fields until do_stepwise_t starts ping-ponging
+    if (sp.alt_buffers) {  // the second pair: a launch's *_in buffers (TallOver::cur says which pair is which)
         a.q1_in = (const T*)carve(vec);
         a.pm_in = (const T*)carve(vec);
         a.part_in = (const T*)carve(pg);
     }
     if (extra_out) *extra_out = carve(extra);
-    a.C = C;
-    a.p = m->p;
-    {
-        // wide float32 models: the exact-split bf16 matrix-core kernels (lr_wide_bf16.h), 4 or 8 waves per workgroup
-        a.wide_bf16 = (m->P > 32 && m->d_xblk) ? wide_engine(m, Cp) : 0;
-        a.xblk = static_cast<const uint16_t*>(m->d_xblk);
-        a.xblk1 = static_cast<const uint16_t*>(m->d_xblk1);
-        a.xblk1h = static_cast<const uint16_t*>(m->d_xblk1h);
-        a.xmx = static_cast<const uint16_t*>(m->d_xmx);
-    }
+    a.wide_bf16 = sp.wide_engine;
+    a.xblk = static_cast<const uint16_t*>(m->d_xblk), a.xmx = static_cast<const uint16_t*>(m->d_xmx);
+    a.xblk1 = static_cast<const uint16_t*>(m->d_xblk1), a.xblk1h = static_cast<const uint16_t*>(m->d_xblk1h);
     return LR_OK;
 }
+// ... and what every sampler adds to it
+template <typename T, int P>
+void sampler_args(const RunSpec& rs, const lr_run_opts* o, void* state, void* out, lr::TallArgs<T, P>* a) {
+    a->state = static_cast<T*>(state);
+    a->out = static_cast<T*>(out);
+    a->chain_offset = o->chain_offset;
+    a->seed = o->seed;
+    a->l = rs.l;
+    fill_tuning<T, P>(rs, a);
+    a->stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+}
+
+// what one launch differs in from the run's argument block; the defaults are an exact kernel on the first buffer pair
+struct TallOver {
+    int cur = 0;           // which of the two (q1, pm, part_g) sets is current: the other one is this launch's (q1_in, pm_in, part_in)
+    int RS = 0;            // slice partials an update sums, where the interior kernel just wrote another count than the exact one (0: the exact)
+    int interior = 0;      // an interior HMC gradient evaluation that runs in reduced precision
+    int part_f32 = 0;      // float64 models: the partials this update reads are float32 (an interior kernel wrote them)
+    int fuse_mid = 0;      // the interior kernel first finishes the previous leapfrog step from the *_in buffers
+    bool stamped = false;  // development builds: the launch records time stamps (lr_stamps.h)
+};
+template <typename T, int P> struct TallRun {
+    const lr::InstTable* t;
+    hipStream_t st;
+    const lr::TallArgs<T, P> base;
+    int rc = 0;  // of the first launch that failed: nothing is launched after it
+    template <typename F> void issue(const TallOver& o, F&& launch) {
+        if (rc) return;
+        lr::TallArgs<T, P> a = base;
+        if (o.cur) {
+            a.q1 = const_cast<T*>(base.q1_in), a.pm = const_cast<T*>(base.pm_in), a.part_g = const_cast<T*>(base.part_in);
+            a.q1_in = base.q1, a.pm_in = base.pm, a.part_in = base.part_g;
+        }
+        if (o.RS) a.RS = o.RS;
+        a.interior = o.interior, a.part_f32 = o.part_f32, a.fuse_mid = o.fuse_mid;
+        if (o.stamped) LR_STAMPS_ARM(a);
+        rc = launch(&a);
+    }
+    void partial(int value, int grad, const TallOver& o = {}) { issue(o, [&](const void* a) { return t->launch_tall_partial(st, value, grad, a); }); }
+    void update(int kind, int phase, int64_t iter, int64_t out_row, int next, const TallOver& o = {}) { issue(o, [&](const void* a) { return t->launch_tall_update(st, kind, phase, iter, out_row, next, a); }); }
+};
 
 // lr_eval through the stepwise engine (tall or wide models): load -> partial(value, grad) -> finish
 template <typename T, int P>
 int do_eval_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, const void* beta, void* ll, void* lprior,
                        void* lpost, void* grad) {
-    if ((C + 63) / 64 > 65535) return fail(LR_ERR_UNSUPPORTED, "the stepwise engine takes at most %lld chains per call (got %lld)", 65535LL * 64, (long long)C);
     lr::TallArgs<T, P> a;
-    int rc = setup_tall<T, P>(m, pl, st, C, C, &a);
+    const int rc = setup_tall<T, P>(m, plan_stepwise(m, pl, -1, 0, LR_PREC_FULL, C), st, C, &a);
     if (rc) return rc;
     a.state = static_cast<T*>(const_cast<void*>(beta));
     a.ev_ll = static_cast<T*>(ll);
     a.ev_lprior = static_cast<T*>(lprior);
     a.ev_lpost = static_cast<T*>(lpost);
     a.ev_grad = static_cast<T*>(grad);
-    const lr::InstTable* t = m->table;
-    rc = t->launch_tall_update(st, lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0, &a);
-    if (!rc) rc = t->launch_tall_partial(st, 1, 1, &a);
-    if (!rc) rc = t->launch_tall_update(st, lr::KIND_HMC, lr::PH_EVAL, 0, -1, 0, &a);
-    if (rc) return fail(LR_ERR_HIP, "stepwise eval launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    TallRun<T, P> run{m->table, st, a};
+    run.update(lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0);
+    run.partial(1, 1);
+    run.update(lr::KIND_HMC, lr::PH_EVAL, 0, -1, 0);
+    if (run.rc) return fail(LR_ERR_HIP, "stepwise eval launch failed (%d): %s", run.rc, hipGetErrorString(hipGetLastError()));
     return LR_OK;
 }
-
-// wide models: two chain tiles per workgroup of the trajectory kernel beyond this many tiles per CU (one tile per workgroup up to it)
-constexpr int kTraj2FromTilesPerCu = 1;
 
 template <typename T, int P>
 int do_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, void* state,
                   double* lp_state, void* out, uint32_t* accepts) {
-    const int64_t C = o->n_chains, Cp = plan_count(o);
-    // (chain blocks of 16 .. 128 chains are the grid's y / x dimension of the partial kernels: y is a 16-bit quantity)
-    if ((C + 63) / 64 > 65535) return fail(LR_ERR_UNSUPPORTED, "the stepwise engine takes at most %lld chains per call (got %lld): split the run into shards (chain_offset)", 65535LL * 64, (long long)C);
-    lr::TallArgs<T, P> a;
-    int rc = setup_tall<T, P>(m, pl, st, C, Cp, &a);
-    if (rc) return rc;
-    a.state = static_cast<T*>(state);
-    a.lp_state = lp_state;
-    a.out = static_cast<T*>(out);
-    a.accepts = accepts;
-    a.C = C;
-    a.chain_offset = o->chain_offset;
-    a.seed = o->seed;
-    a.p = m->p;
-    a.l = rs.l;
-    a.step = (T)rs.step;
-    for (int j = 0; j < P; ++j) {
-        a.a[j] = (T)rs.a[j];
-        a.b[j] = (T)rs.b[j];
-        a.c[j] = (T)rs.c[j];
-    }
-    a.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
-    const lr::InstTable* t = m->table;
-    auto U = [&](int phase, int64_t iter, int64_t out_row, int bn) {
-        if (!rc) rc = t->launch_tall_update(st, rs.kind, phase, iter, out_row, bn, &a);
-    };
-    auto K = [&](int v, int g) {
-        if (!rc) rc = t->launch_tall_partial(st, v, g, &a);
-    };
-    // interior leapfrog gradients (HMC): reduced precision where the policy allows and a kernel exists
-    const bool bf16_interior = rs.kind == lr::KIND_HMC && o->precision != LR_PREC_FULL &&
-                               (m->d_xblk1 != nullptr || m->d_xmx != nullptr);
-    const int RS_exact = a.RS, RS_mid = bf16_interior && a.RS_i > 0 ? a.RS_i : a.RS;
-    if (!bf16_interior) a.RS_i = 0;
-    auto KI = [&]() {
-        a.interior = bf16_interior ? 1 : 0;
-        LR_STAMPS_ARM(a);
-        K(0, 1);
-        LR_STAMPS_DISARM(a);
-        a.interior = 0;
-    };
-    // wide models: the whole interior of a trajectory in one launch (k_wide_traj2_bf16): no slice partials, no update launches.  One
-    // workgroup streams the whole design per step.  With two chain tiles per workgroup it wins at every chain count from one tile per CU
-    // up (us per evaluation, launch per step | trajectory kernel: 12 288 chains 79.6 | 49.6, 16 384: 67.5 | 51.4, 32 768: 120.6 | 101.6,
-    // 65 536: 235.9 | 202.7; profiles/r5_cfg5_whole.txt); below that, with one tile per workgroup, by the measured rule further down.
-    // LOGREG_DEBUG_OPTS wide_traj=1 / 2 force it with one / two tiles per workgroup, wide_traj=0 forbids it.
-    const int64_t traj_tiles = (Cp + 15) / 16;
-    // Two chain tiles per workgroup (the same trajectories bit for bit) from the chain count at which one tile per workgroup needs a
-    // second round of workgroups.
-    // LR_PREC_BF16 (the caller's explicit request for the cheapest interior force): beta in ONE bf16 piece, on the two-tile kernel at any
-    // tile count the trajectory path takes -- a third of the MFMAs fewer for ~0.02 of acceptance (lr_wide_bf16.h)
-    const bool one_piece = o->precision == LR_PREC_BF16 && m->dbg.wide_traj != 1 && traj_tiles > (int64_t)kTraj2FromTilesPerCu * m->cus;  // (where the two-tile kernel runs anyway; 4096 chains: 16.6 against 16.9 us on the one-tile kernel -- nothing to buy)
-    const bool half_ok = m->d_xblk1h != nullptr && m->dbg.wide_f16 != 0;
-    // Operand format of every reduced-precision interior kernel of a wide model: rows and beta in ONE f16 piece each where the rows fit f16
-    // (11 significant bits against bf16's 8: closer to the exact force than bf16 rows x two bf16 pieces of beta, with a third of the MFMAs
-    // fewer -- config 5 whole: 23.9 -> 20.9 us per evaluation, acceptance 0.756 -> 0.758 = the exact interior's), else the bf16 pieces.
-    a.traj_fmt = m->dbg.wide_f16 == 2 && half_ok ? 2 : one_piece ? 1 : (half_ok ? 2 : 0);
-    a.traj_tiles = (m->dbg.wide_traj == 2 || one_piece) ? 2 : (m->dbg.wide_traj == 1 ? 1 : (traj_tiles > (int64_t)kTraj2FromTilesPerCu * m->cus ? 2 : 1));
-    // Below one chain tile per CU the kernel runs with ONE tile per workgroup (k_wide_traj2_bf16<.., 1>; round 5: it replaced round 3's
-    // one-tile kernel -- the same trajectories bit for bit, 1.1 - 1.5 x faster).  Its step costs what streaming the image through one
-    // CU costs, whatever the chain count; the launch-per-step kernels split the rows over workgroups but pay the launch boundary and the
-    // partial hand-over, and degrade from half the chip's tiles up (us per evaluation, trajectory | launch per step, tools/traj_rule_check.py:
-    // p=128 n=2000 (500 KB) 1024 chains 5.6 | 7.3; n=3000 (750 KB) 7.3 | 8.0; n=4096 (1 MB) 9.2 | 8.8 at 1024 chains, 10.2 | 12.0 at 2048,
-    // 12.1 | 15.8 at 3072; p=64 n=3000 (375 KB) 5.3 | 5.6; n=5000 (625 KB) 7.8 | 6.5 at 1024 chains; n=8000 (1000 KB) 11.6 | 8.0).
-    const int64_t image_bytes = (int64_t)m->n * m->P * 2;
-    const bool traj = P > 32 && bf16_interior && m->d_xblk1 != nullptr && t->launch_tall_traj != nullptr && rs.l > 1 &&
-                      m->dbg.wide_traj != 0 &&
-                      (m->dbg.wide_traj >= 1 || traj_tiles >= m->cus ||
-                       (traj_tiles >= m->cus / 2 && image_bytes <= (P == 128 ? 1024 : 768) * 1024) ||  // (p = 64, n = 8000 at 2048 chains: 12.6 | 11.5)
-                       (traj_tiles >= 3 * m->cus / 4 && image_bytes <= 1024 * 1024) ||
-                       image_bytes <= 512 * 1024 || (P == 128 && image_bytes <= 768 * 1024));
-    const bool fuse = bf16_interior && a.RS_i > 0 &&
-                      ((P > 32 && a.RS_i <= 4) ||                                            // kFuseSlices (lr_wide_bf16.h)
-                       (P <= 32 && a.rowsplit_waves == 16 && a.RS_i <= 16 && m->d_xmx));   // kMx16FuseSlices (lr_tall_mx.h)
-    T* qb[2] = {a.q1, const_cast<T*>(a.q1_in)};
-    T* pb[2] = {a.pm, const_cast<T*>(a.pm_in)};
-    T* gb[2] = {a.part_g, const_cast<T*>(a.part_in)};
-    int cs = 0, cg = 0;  // which of the pairs holds the current state / the latest partials
     const int kind = rs.kind;
-    U(lr::PH_LOAD, 0, -1, 0);
-    if (kind == lr::KIND_HMC) K(1, 1);
-    else if (kind != lr::KIND_RWMH) K(0, 1);
-    U(lr::PH_INIT, o->iter_offset, -1, 0);
+    const StepwisePlan sp = plan_stepwise(m, pl, kind, rs.l, o->precision, plan_count(o));
+    lr::TallArgs<T, P> a;
+    const int rc = setup_tall<T, P>(m, sp, st, o->n_chains, &a);
+    if (rc) return rc;
+    sampler_args<T, P>(rs, o, state, out, &a);
+    a.lp_state = lp_state;
+    a.accepts = accepts;
+    TallRun<T, P> run{m->table, st, a};
+    // The launches of this run, each with all it differs in.  `cur` moves only on PATH_FUSED; where it stands when a trajectory ends
+    // is where the next one, PH_END and PH_STORE find the state.
+    int cur = 0;
+    auto exact = [&] { TallOver v; v.cur = cur; return v; };
+    auto interior = [&](int fused) {  // an interior leapfrog gradient: reduced precision where the plan says so
+        TallOver v = exact();
+        v.interior = sp.bf16_interior, v.fuse_mid = fused, v.stamped = true;
+        return v;
+    };
+    auto mid = [&] {  // the update behind interior steps: as many slice partials as the interior kernel wrote, float32 ones on a float64 model
+        TallOver v = exact();
+        v.RS = sp.RS_mid(), v.part_f32 = sizeof(T) == 8 && sp.bf16_interior;
+        return v;
+    };
+    run.update(kind, lr::PH_LOAD, 0, -1, 0);
+    if (kind == lr::KIND_HMC) run.partial(1, 1);
+    else if (kind != lr::KIND_RWMH) run.partial(0, 1);
+    run.update(kind, lr::PH_INIT, o->iter_offset, -1, 0);
     const int64_t total = o->iters * o->thin;
-    for (int64_t tt = 0; tt < total && !rc; ++tt) {
-        if (kind == lr::KIND_HMC) {
-            if (traj) {
-                LR_STAMPS_ARM(a);
-                if (!rc) rc = t->launch_tall_traj(st, &a);
-                LR_STAMPS_DISARM(a);
-            } else if (fuse) {
-                // row-split interior kernel: every launch but the first finishes the previous leapfrog step in its
-                // own prologue (state and partial buffers ping-pong), so the L - 1 interior steps are L - 1
-                // launches plus ONE update at the end instead of 2 (L - 1) launches
-                for (int i = 0; i < rs.l - 1; ++i) {
-                    if (i > 0) {
-                        a.q1_in = qb[cs];
-                        a.pm_in = pb[cs];
-                        a.part_in = gb[cg];
-                        cs ^= 1;
-                        cg ^= 1;
-                        a.q1 = qb[cs];
-                        a.pm = pb[cs];
-                        a.part_g = gb[cg];
-                    }
-                    a.fuse_mid = i > 0;
-                    KI();
-                    a.fuse_mid = 0;
-                }
-                if (rs.l > 1) {
-                    a.RS = RS_mid;
-                    a.part_f32 = sizeof(T) == 8;  // (float64 models: the interior kernel's partials are float32)
-                    U(lr::PH_MID, 0, -1, 0);
-                    a.part_f32 = 0;
-                    a.RS = RS_exact;
-                }
-            } else {
-                for (int i = 0; i < rs.l - 1; ++i) {
-                    KI();
-                    a.RS = RS_mid;  // the update sums as many slice partials as the partial kernel just wrote
-                    a.part_f32 = sizeof(T) == 8 && bf16_interior;  // (float64 models: those partials are float32)
-                    U(lr::PH_MID, 0, -1, 0);
-                    a.part_f32 = 0;
-                    a.RS = RS_exact;
-                }
+    const int steps = kind == lr::KIND_HMC ? rs.l - 1 : 0;  // interior leapfrog steps of an iteration
+    for (int64_t tt = 0; tt < total && !run.rc; ++tt) {
+        if (sp.path == PATH_TRAJ) {  // (planned for HMC with L > 1 only)
+            TallOver v = exact();
+            v.stamped = true;
+            run.issue(v, [&](const void* p) { return m->table->launch_tall_traj(st, p); });
+        } else if (sp.path == PATH_FUSED) {
+            for (int i = 0; i < steps; ++i) {
+                if (i > 0) cur ^= 1;  // the launch reads the step it finishes from the pair the previous launch wrote
+                run.partial(0, 1, interior(i > 0));
             }
-            K(1, 1);
-        } else if (kind == lr::KIND_MALA) {
-            K(1, 1);
-        } else if (kind == lr::KIND_RWMH) {
-            K(1, 0);
-        } else {
-            K(0, 1);
+            if (steps > 0) run.update(kind, lr::PH_MID, 0, -1, 0, mid());
+        } else {  // PATH_PER_STEP, PATH_EXACT
+            for (int i = 0; i < steps; ++i) {
+                run.partial(0, 1, interior(0));
+                run.update(kind, lr::PH_MID, 0, -1, 0, mid());
+            }
         }
+        if (kind == lr::KIND_HMC || kind == lr::KIND_MALA) run.partial(1, 1, exact());
+        else if (kind == lr::KIND_RWMH) run.partial(1, 0, exact());
+        else run.partial(0, 1, exact());
         const int64_t out_row = ((tt + 1) % o->thin == 0) ? (tt + 1) / o->thin - 1 : -1;
-        U(lr::PH_END, o->iter_offset + tt, out_row, tt + 1 < total);
+        run.update(kind, lr::PH_END, o->iter_offset + tt, out_row, tt + 1 < total, exact());
     }
-    U(lr::PH_STORE, 0, -1, 0);
-    if (rc) return fail(LR_ERR_HIP, "stepwise launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    run.update(kind, lr::PH_STORE, 0, -1, 0, exact());
+    if (run.rc) return fail(LR_ERR_HIP, "stepwise launch failed (%d): %s", run.rc, hipGetErrorString(hipGetLastError()));
     return LR_OK;
 }
 
@@ -387,50 +324,37 @@ int do_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs
 // the leaf's update launch.  The one thing the host learns from the device is how many chains are still building, read at the end of
 // a doubling on the caller's stream (at most max_depth - 1 waits per iteration); zero ends the iteration.  The loop is bounded by
 // 2^max_depth - 1 leaves whatever it reads, and a finished chain is inert, so the results do not depend on when the host looks.
+// Full precision at every leaf: the plan of a NUTS run is PATH_EXACT.
 template <typename T, int P>
 int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, int max_depth, void* state, void* out,
                        void* counters, int8_t* depth_out) {
-    const int64_t C = o->n_chains, Cp = plan_count(o);
-    if ((C + 63) / 64 > 65535) return fail(LR_ERR_UNSUPPORTED, "the stepwise engine takes at most %lld chains per call (got %lld): split the run into shards (chain_offset)", 65535LL * 64, (long long)C);
+    const int64_t C = o->n_chains;
     const lr::InstTable* t = m->table;
     if (!t->launch_tall_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
     const lr::NutsTallCarve cv = lr::nuts_tall_carve(C, P, sizeof(T), max_depth);
     lr::TallArgs<T, P> a;
     unsigned char* w = nullptr;
-    int rc = setup_tall<T, P>(m, pl, st, C, Cp, &a, cv.total, &w);
+    const int rc = setup_tall<T, P>(m, plan_stepwise(m, pl, LR_KIND_NUTS, 0, o->precision, plan_count(o)), st, C, &a, cv.total, &w);
     if (rc) return rc;
-    a.RS_i = 0;  // full precision at every leaf: no reduced-precision interior, no trajectory kernel
-    a.state = static_cast<T*>(state);
-    a.out = static_cast<T*>(out);
-    a.chain_offset = o->chain_offset;
-    a.seed = o->seed;
-    a.step = (T)rs.step;
-    for (int j = 0; j < P; ++j) {
-        a.a[j] = (T)rs.a[j];
-        a.b[j] = (T)rs.b[j];
-        a.c[j] = (T)rs.c[j];
-    }
-    a.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    sampler_args<T, P>(rs, o, state, out, &a);
+    TallRun<T, P> run{t, st, a};
     const lr::NutsTallArgs<T> na{reinterpret_cast<T*>(w + cv.vec_off), reinterpret_cast<lr::NutsTallChain*>(w + cv.chain_off), reinterpret_cast<uint32_t*>(w + cv.tally_off),
                                  static_cast<lr::NutsCounters*>(counters), depth_out, max_depth};
-    auto K = [&]() {
-        if (!rc) rc = t->launch_tall_partial(st, 1, 1, &a);
-    };
     auto N = [&](int phase, int64_t iter, const lr::NutsStep& leaf, int64_t out_row, int flag) {
-        if (!rc) rc = t->launch_tall_nuts(st, &a, &na, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag);
+        run.issue({}, [&](const void* p) { return t->launch_tall_nuts(st, p, &na, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag); });
     };
     const lr::NutsStep none{};
-    if (!rc) rc = t->launch_tall_update(st, lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0, &a);
-    K();
+    run.update(lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0);
+    run.partial(1, 1);
     N(lr::NPH_BEGIN, o->iter_offset, none, -1, 1);
     const int64_t total = o->iters * o->thin;
-    for (int64_t tt = 0; tt < total && !rc; ++tt) {
-        for (lr::NutsSched sch(max_depth); !sch.done() && !rc;) {
+    for (int64_t tt = 0; tt < total && !run.rc; ++tt) {
+        for (lr::NutsSched sch(max_depth); !sch.done() && !run.rc;) {
             const lr::NutsStep leaf = sch.cur();
-            K();
+            run.partial(1, 1);
             N(lr::NPH_LEAF, o->iter_offset + tt, leaf, -1, leaf.read);
             uint32_t building = 1;
-            if (leaf.read && !rc) {
+            if (leaf.read && !run.rc) {
                 if (hipMemcpyAsync(&building, na.tally + leaf.d, sizeof(building), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
                     return fail(LR_ERR_HIP, "NUTS: reading the tally of building chains failed: %s", hipGetErrorString(hipGetLastError()));
             }
@@ -440,7 +364,7 @@ int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpe
         N(lr::NPH_END, o->iter_offset + tt, none, out_row, tt + 1 < total);
     }
     N(lr::NPH_STORE, 0, none, -1, 0);
-    if (rc) return fail(LR_ERR_HIP, "stepwise NUTS launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    if (run.rc) return fail(LR_ERR_HIP, "stepwise NUTS launch failed (%d): %s", run.rc, hipGetErrorString(hipGetLastError()));
     return LR_OK;
 }
 

@@ -82,10 +82,10 @@ struct DebugOpts {
     int residency_cap = 1;  // 0: fused chain kernels without the LDS request that spreads a grid evenly over the CUs (lr_inst.h)
     int tall_mx16 = 1;      // 0: tall models run their interior leapfrog steps on the 4-wave kernel with separate update launches
                             //    instead of the 16-wave kernel that finishes the previous step in its prologue (lr_tall_mx.h)
-    int wide_traj = -1;     // wide models: 1 / 2 force the one-launch trajectory kernel with 1 / 2 chain tiles per workgroup, 0 forbids it (-1: by chain count; lr_engine.h)
+    int wide_traj = -1;     // wide models: 1 / 2 force the one-launch trajectory kernel with 1 / 2 chain tiles per workgroup, 0 forbids it (-1: by chain count; lr_plan.h)
     int wide_waves = 0;     // wide models: 4 | 8 waves (64 | 128 chains) per workgroup of the exact and chain-split kernels (0: by chain count)
     int wide_f16 = 1;       // wide models: 0 keeps the bf16 two-piece interior where the rows fit the one-piece f16 format, 2 uses f16 also
-                            //    where LR_PREC_BF16 would take bf16 x one piece (lr_engine.h)
+                            //    where LR_PREC_BF16 would take bf16 x one piece (lr_plan.h)
     bool is_default() const { return residency_cap == 1 && tall_mx16 == 1 && wide_traj == -1 && wide_waves == 0 && wide_f16 == 1; }
 };
 // returns false (and names the culprit) on an unknown key or a value outside its range

@@ -7,6 +7,7 @@
 // a table cannot know: which variants this build instantiates and whether a variant's operands fit its store (registers,
 // LDS, the device-memory images the model carries).  tests/test_gpu_planner.py times AUTO against every forced alternative
 // at shapes on both sides of the table's boundaries and fails when AUTO is more than 10 % off the best.
+// plan_stepwise() then decides how a run on the stepwise engine is launched (StepwisePlan); lr_engine.h only states those launches.
 #pragma once
 #include "../../include/logreg_hip_nuts.h"  // LR_KIND_NUTS (plan_run)
 #include "../../include/logreg_hip_pg.h"    // LR_KIND_PG
@@ -616,11 +617,37 @@ int check_group_for(const lr_model* m, int group, int mode) {
     return LR_OK;
 }
 
-// Row slices of the reduced-precision INTERIOR leapfrog steps of the stepwise engine (HMC, precision policy permitting): how many
-// slices RS_i of how many rows, and the workgroup shape of the kernel that takes them (waves: 4 / 8 row-split waves of the wide
-// kernel, 4 or 16 waves of the tall matrix-pipe kernel).  RS_i = 0: no interior kernel for this model (the exact kernels run every
-// step).  Cp: the chain count the run is planned for (lr_run_opts.plan_chains).
+// ---------------------------------------------------------------------------------------------------------------------------
+// How a run on the stepwise engine is launched (lr_engine.h states the launches and decides nothing): the slicing of the exact
+// kernels (from the Plan), the slicing of the reduced-precision interior leapfrog steps, and which of the four interior paths an HMC
+// trajectory takes.  Pure host code, one call per run; tests/test_planner_cpu.py pins its choices, tests/test_stepwise_trace_cpu.py
+// the launches that follow from them.
+enum InteriorPath {
+    PATH_EXACT,     // no reduced-precision interior: the exact partial kernel + a PH_MID update per interior step
+    PATH_PER_STEP,  // an interior partial launch + a PH_MID update per step
+    PATH_FUSED,     // the update folded into the next launch's prologue (state and partial buffers ping-pong), then ONE PH_MID
+    PATH_TRAJ       // wide models: all L - 1 interior steps of a trajectory in one launch
+};
+// Row slices of the interior kernels: how many slices RS_i of how many rows, and the workgroup shape of the kernel that takes them
+// (waves: 4 / 8 row-split waves of the wide kernel, 4 or 16 waves of the tall matrix-pipe kernel).  RS_i = 0: no row-split
+// interior kernel for this model and chain count.  A property of (model, chains): the same whatever the kind and precision.
 struct InteriorPlan { int RS_i; int64_t slice_len_i; int waves; };
+struct StepwisePlan : InteriorPlan {
+    int RS; int64_t slice_len;  // the exact kernels' row slices (Plan.G, Plan.R)
+    int wide_engine;            // wide float32 models: 1 = 4 waves (64 chains) per workgroup of the exact kernels, 2 = 8 waves; else 0
+    bool bf16_interior;         // interior leapfrog gradients in reduced precision: HMC, the policy allows it and a kernel exists
+    InteriorPath path;
+    int traj_tiles, traj_fmt;   // lr::TallArgs: chain tiles per workgroup of the trajectory kernel, operand format of the wide interior kernels
+    bool alt_buffers;           // the workspace carries a second (q1, pm) pair and a second partial buffer (PATH_FUSED ping-pongs)
+    int RS_mid() const { return bf16_interior && RS_i > 0 ? RS_i : RS; }  // slice partials a PH_MID update sums
+};
+
+// wide models: two chain tiles per workgroup of the trajectory kernel beyond this many tiles per CU (one tile per workgroup up to it)
+constexpr int kTraj2FromTilesPerCu = 1;
+// rows and beta of a wide model's interior kernels in ONE f16 piece each: where the rows fit f16 (lr_model_create built the image)
+bool interior_f16(const lr_model* m) { return m->d_xblk1h != nullptr && m->dbg.wide_f16 != 0; }
+
+// Cp: the chain count the run is planned for (lr_run_opts.plan_chains).  Called by plan_stepwise alone.
 InteriorPlan plan_interior(const lr_model* m, int64_t Cp) {
     int RS_i = 0, rs_waves = 4;
     int64_t slice_len_i = 0;
@@ -669,5 +696,53 @@ InteriorPlan plan_interior(const lr_model* m, int64_t Cp) {
     return InteriorPlan{RS_i, slice_len_i, rs_waves};
 }
 
+// kind: LR_KIND_* of the run (lr_eval: -1; NUTS evaluates every leaf exactly);  l: leapfrog steps per trajectory;  precision: LR_PREC_*
+StepwisePlan plan_stepwise(const lr_model* m, const Plan& pl, int kind, int l, int precision, int64_t Cp) {
+    StepwisePlan sp{};
+    sp.RS = pl.G, sp.slice_len = pl.R;
+    sp.wide_engine = (m->P > 32 && m->d_xblk) ? wide_engine(m, Cp) : 0;
+    static_cast<InteriorPlan&>(sp) = plan_interior(m, Cp);
+    sp.alt_buffers = sp.RS_i > 0 && (m->P > 32 || sp.waves == 16);
+    sp.bf16_interior = kind == LR_KIND_HMC && precision != LR_PREC_FULL && (m->d_xblk1 != nullptr || m->d_xmx != nullptr);
+    // wide models: the whole interior of a trajectory in one launch (k_wide_traj2_bf16): no slice partials, no update launches.  One
+    // workgroup streams the whole design per step.  With two chain tiles per workgroup it wins at every chain count from one tile per CU
+    // up (us per evaluation, launch per step | trajectory kernel: 12 288 chains 79.6 | 49.6, 16 384: 67.5 | 51.4, 32 768: 120.6 | 101.6,
+    // 65 536: 235.9 | 202.7; profiles/r5_cfg5_whole.txt); below that, with one tile per workgroup, by the measured rule further down.
+    // LOGREG_DEBUG_OPTS wide_traj=1 / 2 force it with one / two tiles per workgroup, wide_traj=0 forbids it.
+    const int64_t tiles = (Cp + 15) / 16;
+    // Two chain tiles per workgroup (the same trajectories bit for bit) from the chain count at which one tile per workgroup needs a
+    // second round of workgroups.
+    const bool two_tiles = tiles > (int64_t)kTraj2FromTilesPerCu * m->cus;
+    // LR_PREC_BF16 (the caller's explicit request for the cheapest interior force): beta in ONE bf16 piece, on the two-tile kernel at any
+    // tile count the trajectory path takes -- a third of the MFMAs fewer for ~0.02 of acceptance (lr_wide_bf16.h)
+    // (where the two-tile kernel runs anyway; 4096 chains: 16.6 against 16.9 us on the one-tile kernel -- nothing to buy)
+    const bool one_piece = precision == LR_PREC_BF16 && m->dbg.wide_traj != 1 && two_tiles;
+    // Operand format of every reduced-precision interior kernel of a wide model: rows and beta in ONE f16 piece each where the rows fit f16
+    // (11 significant bits against bf16's 8: closer to the exact force than bf16 rows x two bf16 pieces of beta, with a third of the MFMAs
+    // fewer -- config 5 whole: 23.9 -> 20.9 us per evaluation, acceptance 0.756 -> 0.758 = the exact interior's), else the bf16 pieces.
+    const bool half_ok = interior_f16(m);
+    sp.traj_fmt = m->dbg.wide_f16 == 2 && half_ok ? 2 : one_piece ? 1 : (half_ok ? 2 : 0);
+    sp.traj_tiles = (m->dbg.wide_traj == 2 || one_piece) ? 2 : (m->dbg.wide_traj == 1 ? 1 : (two_tiles ? 2 : 1));
+    // Below one chain tile per CU the kernel runs with ONE tile per workgroup (k_wide_traj2_bf16<.., 1>; round 5: it replaced round 3's
+    // one-tile kernel -- the same trajectories bit for bit, 1.1 - 1.5 x faster).  Its step costs what streaming the image through one
+    // CU costs, whatever the chain count; the launch-per-step kernels split the rows over workgroups but pay the launch boundary and the
+    // partial hand-over, and degrade from half the chip's tiles up (us per evaluation, trajectory | launch per step, tools/traj_rule_check.py:
+    // p=128 n=2000 (500 KB) 1024 chains 5.6 | 7.3; n=3000 (750 KB) 7.3 | 8.0; n=4096 (1 MB) 9.2 | 8.8 at 1024 chains, 10.2 | 12.0 at 2048,
+    // 12.1 | 15.8 at 3072; p=64 n=3000 (375 KB) 5.3 | 5.6; n=5000 (625 KB) 7.8 | 6.5 at 1024 chains; n=8000 (1000 KB) 11.6 | 8.0).
+    const int64_t image_bytes = (int64_t)m->n * m->P * 2;
+    const bool traj = m->P > 32 && sp.bf16_interior && m->d_xblk1 != nullptr && m->table->launch_tall_traj != nullptr && l > 1 &&
+                      m->dbg.wide_traj != 0 &&
+                      (m->dbg.wide_traj >= 1 || tiles >= m->cus ||
+                       (tiles >= m->cus / 2 && image_bytes <= (m->P == 128 ? 1024 : 768) * 1024) ||  // (p = 64, n = 8000 at 2048 chains: 12.6 | 11.5)
+                       (tiles >= 3 * m->cus / 4 && image_bytes <= 1024 * 1024) ||
+                       image_bytes <= 512 * 1024 || (m->P == 128 && image_bytes <= 768 * 1024));
+    // row-split interior kernels: every launch but the first finishes the previous leapfrog step in its own prologue, so the L - 1
+    // interior steps are L - 1 launches plus ONE update at the end instead of 2 (L - 1) launches -- while the prologue can sum the slices
+    const bool fuse = sp.bf16_interior && sp.RS_i > 0 &&
+                      ((m->P > 32 && sp.RS_i <= 4) ||                                     // kFuseSlices (lr_wide_bf16.h)
+                       (m->P <= 32 && sp.waves == 16 && sp.RS_i <= 16 && m->d_xmx));    // kMx16FuseSlices (lr_tall_mx.h)
+    sp.path = !sp.bf16_interior ? PATH_EXACT : traj ? PATH_TRAJ : fuse ? PATH_FUSED : PATH_PER_STEP;
+    return sp;
+}
 
 }  // namespace

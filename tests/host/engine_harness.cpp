@@ -10,6 +10,8 @@
 // allocation of create, accumulate and result.
 //   engine_harness all        every scenario on one thread
 //   engine_harness threads    two host threads, one model / stream / chain set each, running concurrently (ThreadSanitizer)
+//   engine_harness trace      the launches of the stepwise engine, case by case, as text (tests/test_stepwise_trace_cpu.py compares it with
+//                             tests/golden/stepwise_launch_trace.txt, recorded from the engine before its launch loop was rewritten)
 #include "logreg_hip.h"
 #include "logreg_hip_acf.h"
 #include "logreg_hip_loo.h"
@@ -22,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <thread>
@@ -41,6 +44,9 @@ void hipstub_fail_malloc_at(long nth);
 void hipstub_set_devices(int n);
 long hipstub_work_on_device(int d);
 long hipstub_wrong_device();
+void hipstub_trace_begin();
+long hipstub_trace_end();
+const char* hipstub_trace_record(long i);
 }
 
 static int g_fail = 0;
@@ -855,6 +861,121 @@ static void scenario_accumulator_errors() {
     hipstub_set_devices(1);
 }
 
+// ---- mode `trace`: which kernels the stepwise engine launches, with which grid, in which order -------------------------------------
+// A line per model ("== dtype n p chains [debug option]") and under it one per case, "<case>: <launches>": a launch is the index of its record (kernel name, grid, block, LDS, stream ordinal)
+// in the table printed at the end, and a run of repeats is folded, innermost first: "(3 4)*7" is seven times launch 3 then launch 4.
+static std::string fold(const std::vector<int>& s, size_t lo, size_t hi) {
+    std::string out;
+    for (size_t i = lo; i < hi;) {
+        size_t bp = 0, br = 1;  // the period and count of the repeat from i on that covers the most launches (ties: the shortest period)
+        for (size_t p = 1; p <= (hi - i) / 2; ++p) {
+            size_t r = 1;
+            while (i + (r + 1) * p <= hi && std::equal(s.begin() + i, s.begin() + i + p, s.begin() + i + r * p)) ++r;
+            if (r > 1 && r * p > br * bp) bp = p, br = r;
+        }
+        if (!out.empty()) out += ' ';
+        if (br > 1) {
+            out += (bp > 1 ? "(" + fold(s, i, i + bp) + ")" : fold(s, i, i + bp)) + "*" + std::to_string(br);
+            i += bp * br;
+        } else {
+            out += std::to_string(s[i++]);
+        }
+    }
+    return out;
+}
+struct Trace {
+    std::vector<std::string> names, records;
+    std::map<std::string, int> name_ix, record_ix;
+    void begin() { hipstub_trace_begin(); }
+    void end(const std::string& label, int rc) {
+        std::vector<int> seq;
+        for (long i = 0, k = hipstub_trace_end(); i < k; ++i) {
+            const std::string rec = hipstub_trace_record(i), name = rec.substr(0, rec.find(' '));
+            if (name_ix.emplace(name, (int)names.size()).second) names.push_back(name);
+            const std::string key = std::to_string(name_ix[name]) + rec.substr(rec.find(' '));
+            if (record_ix.emplace(key, (int)records.size()).second) records.push_back(key);
+            seq.push_back(record_ix[key]);
+        }
+        if (rc != LR_OK) std::printf("%s: status %d\n", label.c_str(), rc);
+        else std::printf("%s: %s\n", label.c_str(), fold(seq, 0, seq.size()).c_str());
+    }
+    void tables() const {
+        for (size_t i = 0; i < records.size(); ++i) std::printf("launch %zu = kernel %s\n", i, records[i].c_str());
+        for (size_t i = 0; i < names.size(); ++i) std::printf("kernel %zu = %s\n", i, names[i].c_str());
+    }
+};
+static void mode_trace() {
+    struct Shape { int64_t n; int p; int64_t C; int dtype; bool small; };
+    const Shape shapes[] = {// the shapes of the planner's trajectory rule and of the tall 16-wave rule (tests/test_planner_cpu.py)
+                            {2000, 128, 1024, LR_F32, false}, {3000, 128, 1024, LR_F32, false}, {4096, 128, 1024, LR_F32, false}, {4096, 128, 2048, LR_F32, false},
+                            {4096, 128, 3072, LR_F32, false}, {4096, 128, 4096, LR_F32, false}, {4096, 128, 8192, LR_F32, false}, {3000, 64, 1024, LR_F32, false},
+                            {5000, 64, 1024, LR_F32, false}, {8000, 64, 2048, LR_F32, false}, {100000, 8, 1024, LR_F32, false}, {100000, 8, 4096, LR_F32, false},
+                            // small ones: tall in both dtypes, and the shapes of test_short_trajectories_on_the_reduced_precision_interior_kernels
+                            {20000, 8, 256, LR_F32, true}, {20000, 8, 256, LR_F64, true}, {900, 128, 70, LR_F32, true}, {900, 128, 70, LR_F64, true}, {2600, 128, 70, LR_F32, true},
+                            {3000, 8, 70, LR_F32, true}, {1500, 20, 70, LR_F32, true}};
+    const char* const precs[] = {"auto", "full", "bf16"};  // LR_PREC_AUTO, _FULL, _BF16
+    Trace tr;
+    void* stream = nullptr;
+    EXPECT(lr_stream_create(0, &stream) == LR_OK, "stream");
+    for (const Shape& s : shapes) {
+        Data d = make_data(s.n, s.p, (unsigned)(s.n + s.p));
+        const size_t es = s.dtype == LR_F32 ? 4 : 8;
+        Dev state((size_t)s.C * d.p * es), out((size_t)2 * s.C * d.p * es), acc((size_t)s.C * sizeof(lr_nuts_counters)), lp((size_t)s.C * 8), depth((size_t)2 * s.C), ll((size_t)3 * s.C * es);
+        EXPECT(state.p && out.p && acc.p && lp.p && depth.p && ll.p, "device buffers");
+        std::vector<double> vec(d.p, 1.0);
+        std::vector<std::string> opts = {""};
+        if (s.p > 32) for (const char* o : {"wide_traj=0", "wide_traj=1", "wide_traj=2", "wide_f16=0", "rows beyond f16"}) opts.push_back(o);
+        else opts.push_back("tall_mx16=0");
+        for (const std::string& opt : opts) {
+            const bool big = opt == "rows beyond f16";  // (not an option: the same rows times 2^17, which the half-precision image refuses)
+            if (big) for (double& x : d.X) x *= 131072.0;
+            setenv("LOGREG_DEBUG_OPTS", big ? "" : opt.c_str(), 1);
+            lr_model* m = nullptr;
+            EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), s.dtype, 0, &m) == LR_OK, "create n=%lld p=%d %s", (long long)s.n, s.p, opt.c_str());
+            if (!m) continue;
+            std::printf("== %s n=%lld p=%d C=%lld [%s]\n", s.dtype == LR_F32 ? "f32" : "f64", (long long)s.n, s.p, (long long)s.C, opt.c_str());
+            lr_run_opts o{};
+            o.n_chains = s.C; o.thin = 2; o.iters = 2; o.seed = 7; o.mode = LR_MODE_STEPWISE; o.on_device = 1; o.stream = stream;
+            for (int L : {1, 2, 3, 4, 8})
+                for (int prec = 0; prec < 3; ++prec) {
+                    o.precision = prec;
+                    tr.begin();
+                    const int rc = lr_run_hmc(m, state.p, 0.01, L, vec.data(), &o, out.p, (uint32_t*)acc.p);
+                    tr.end("L=" + std::to_string(L) + " " + precs[prec], rc);
+                }
+            o.precision = LR_PREC_AUTO;
+            if (s.small && opt.empty()) {  // the other families, lr_eval and NUTS; a shard planned as a larger run
+                tr.begin();
+                int rc = lr_run_rwmh(m, state.p, (double*)lp.p, vec.data(), &o, out.p, (uint32_t*)acc.p);
+                tr.end("rwmh", rc);
+                tr.begin();
+                rc = lr_run_mala(m, state.p, (double*)lp.p, 1e-3, vec.data(), &o, out.p, (uint32_t*)acc.p);
+                tr.end("mala", rc);
+                tr.begin();
+                rc = lr_run_ul(m, state.p, 1e-3, vec.data(), &o, out.p, (uint32_t*)acc.p);
+                tr.end("ul", rc);
+                tr.begin();
+                rc = lr_eval(m, state.p, ll.p, (char*)ll.p + s.C * es, (char*)ll.p + 2 * s.C * es, out.p, &o);
+                tr.end("eval", rc);
+                tr.begin();
+                rc = lr_run_nuts(m, state.p, 0.01, 3, vec.data(), &o, out.p, (lr_nuts_counters*)acc.p, (int8_t*)depth.p);
+                tr.end("nuts depth 3", rc);
+            }
+            if (opt.empty()) {
+                lr_run_opts sh = o;
+                sh.n_chains = s.C / 2; sh.chain_offset = s.C / 4; sh.plan_chains = (int32_t)(8 * s.C); sh.plan_first = 0;
+                tr.begin();
+                const int rc = lr_run_hmc(m, state.p, 0.01, 4, vec.data(), &sh, out.p, (uint32_t*)acc.p);
+                tr.end("L=4 auto, half the chains of a run planned for 8 x as many", rc);
+            }
+            lr_model_destroy(m);
+        }
+    }
+    unsetenv("LOGREG_DEBUG_OPTS");
+    EXPECT(lr_stream_sync(0, stream) == LR_OK && lr_stream_destroy(0, stream) == LR_OK, "stream destroy");
+    tr.tables();
+}
+
 static void thread_body(int id, int* fails) {
     const Data d = id == 0 ? make_data(200, 8, 21) : make_data(600, 64, 22);
     lr_model* m = nullptr;
@@ -886,6 +1007,8 @@ int main(int argc, char** argv) {
         a.join();
         b.join();
         EXPECT(f0 == 0 && f1 == 0, "thread failures %d %d", f0, f1);
+    } else if (what == "trace") {
+        mode_trace();
     } else {
         scenario_models();
         scenario_forced_variants();

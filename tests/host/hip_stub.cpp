@@ -5,7 +5,8 @@
 // "sanitizers").  "Device" memory is malloc'ed (so an out-of-bounds copy, a use after free, a double free or a leak of a device
 // buffer is an ASan / LSan finding), streams and events are heap objects, a kernel launch validates its configuration and its
 // stream and does nothing else.  The stub also keeps books the harness reads through hipstub_*: launches per stream, waits on
-// events that were never recorded, objects alive -- and can make the N-th hipMalloc fail (cleanup paths of lr_model_create).
+// events that were never recorded, objects alive -- and can make the N-th hipMalloc fail (cleanup paths of lr_model_create).  Switched
+// on, it also keeps a TRACE of the launches: registered kernel name, grid, block, dynamic LDS and stream, in order (hipstub_trace_*).
 // Nothing in the product links this file.
 #include <hip/hip_runtime_api.h>
 
@@ -17,6 +18,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <vector>
 
 namespace {
 
@@ -34,6 +36,9 @@ std::atomic<long> g_work_on_device[8];  // allocations, stream / event creations
 std::atomic<long> g_wrong_device{0};    // work on a stream / an event / memory of ANOTHER device than the current one
 std::map<void*, int> g_alloc_device;
 int g_devices = 1;
+bool g_tracing = false;           // (under g_mu, as the records)
+std::vector<std::string> g_trace;  // one launch per record: "<mangled kernel name> <grid x,y,z> <block x,y,z> <LDS bytes> s<stream ordinal>"
+std::vector<hipStream_t> g_trace_streams;  // the ordinal of a stream: its position in order of first use since the trace began
 thread_local hipError_t t_last = hipSuccess;
 thread_local int t_device = 0;
 thread_local struct { dim3 grid, block; size_t shmem; hipStream_t stream; } t_cfg;
@@ -78,6 +83,21 @@ long hipstub_work_on_device(int d) { return d >= 0 && d < 8 ? g_work_on_device[d
 long hipstub_wrong_device() { return g_wrong_device.load(); }  // a launch / record / copy that touched another device's stream, event or memory
 void hipstub_fail_malloc_at(long nth) { g_fail_at = nth; }  // the nth hipMalloc FROM NOW (1 = the next) fails once; -1: never
 void hipstub_set_devices(int n) { g_devices = n; }
+void hipstub_trace_begin() {  // forget the trace so far and record from here
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_tracing = true;
+    g_trace.clear();
+    g_trace_streams.clear();
+}
+long hipstub_trace_end() {  // stop recording; -> records held (read with hipstub_trace_record until the next begin)
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_tracing = false;
+    return (long)g_trace.size();
+}
+const char* hipstub_trace_record(long i) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return i >= 0 && i < (long)g_trace.size() ? g_trace[(size_t)i].c_str() : nullptr;
+}
 }
 
 // ---- registration of the code objects (the fat binary of every translation unit registers itself at load time)
@@ -112,7 +132,16 @@ extern "C" hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, voi
     if (stream) ++reinterpret_cast<Stream*>(stream)->launches; else ++g_null_launches;
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_kernels.find(fn);
-    ++g_launch_by_kernel[it == g_kernels.end() ? "?" : it->second];
+    const std::string name = it == g_kernels.end() ? "?" : it->second;
+    ++g_launch_by_kernel[name];
+    if (g_tracing) {
+        size_t ord = 0;
+        while (ord < g_trace_streams.size() && g_trace_streams[ord] != stream) ++ord;
+        if (ord == g_trace_streams.size()) g_trace_streams.push_back(stream);
+        char cfg[128];
+        std::snprintf(cfg, sizeof cfg, " %u,%u,%u %u,%u,%u %zu s%zu", grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem, ord);
+        g_trace.push_back(name + cfg);
+    }
     return hipSuccess;
 }
 

@@ -4,8 +4,11 @@
 // GPU-less build container instead of with metered GPU minutes.
 //   stdin:  one request per line   dtype(0|1) p n chains kind(0 rwmh,1 mala,2 hmc,3 ul) precision(0 auto,1 full,2 bf16) group mode cus
 //   stdout: one line per request   "<mode> <group> <rows_per_lane> <lds_bytes> <RS_i> <slice_len_i> <waves_i> <split> <tail_group> <tail_rows> <tail_mode>"   or   "ERR <status> <message>"
-//           (the last three: lr_plan.h plan_interior -- row slices of the reduced-precision interior leapfrog steps of the stepwise
-//            engine for this model and chain count; RS_i = 0: none)
+//           (RS_i, slice_len_i, waves_i: lr_plan.h plan_stepwise -- row slices of the reduced-precision interior leapfrog steps of the
+//            stepwise engine for this model and chain count; RS_i = 0: none)
+//   plan_harness stepwise: how a run on the stepwise engine is launched (lr_plan.h plan_stepwise), every field of the StepwisePlan
+//   stdin:  dtype p n chains kind(as above, 4 nuts) L precision rows_fit_f16(0|1) wide_traj(-1|0|1|2) wide_f16(0|1|2) tall_mx16(0|1) wide_waves(0|4|8) cus
+//   stdout: "<RS> <slice_len> <wide_engine> <RS_i> <slice_len_i> <waves_i> <bf16_interior> <path: 0 exact, 1 per step, 2 fused, 3 traj> <traj_tiles> <traj_fmt> <alt_buffers>"
 #include "lr_model.h"
 
 #include "lr_kernels.h"
@@ -49,11 +52,20 @@ static int f16_modes(const char* mode) {
 }
 
 int main(int argc, char** argv) {
-    if (argc > 1) return f16_modes(argv[1]);
-    int dtype, p, kind, prec, group, mode, cus;
+    const bool stepwise = argc > 1 && !std::strcmp(argv[1], "stepwise");
+    if (argc > 1 && !stepwise) return f16_modes(argv[1]);
+    int dtype, p, kind, prec, group = 0, mode = LR_MODE_STEPWISE, cus, L = 0, fits = 0;
     long long n, chains;
-    while (std::scanf("%d %d %lld %lld %d %d %d %d %d", &dtype, &p, &n, &chains, &kind, &prec, &group, &mode, &cus) == 9) {
+    DebugOpts dbg;
+    auto next = [&] {
+        if (stepwise)
+            return std::scanf("%d %d %lld %lld %d %d %d %d %d %d %d %d %d", &dtype, &p, &n, &chains, &kind, &L, &prec, &fits, &dbg.wide_traj, &dbg.wide_f16, &dbg.tall_mx16,
+                              &dbg.wide_waves, &cus) == 13;
+        return std::scanf("%d %d %lld %lld %d %d %d %d %d", &dtype, &p, &n, &chains, &kind, &prec, &group, &mode, &cus) == 9;
+    };
+    while (next()) {
         lr_model m;
+        m.dbg = dbg;
         m.dtype = dtype;
         m.n = n;
         m.p = p;
@@ -72,6 +84,7 @@ int main(int argc, char** argv) {
         m.d_xms = im.mf_end && model_wants_xms(&m) && m.table->mfma_image_bytes ? yes : nullptr;
         m.d_xblk = im.wide ? yes : nullptr;
         m.d_xblk1 = im.wide1 ? yes : nullptr;
+        m.d_xblk1h = im.wide1 && fits ? yes : nullptr;
         Plan pl{};
         int rc = check_group_for(&m, group, mode);
         lr_run_opts o{};
@@ -79,9 +92,13 @@ int main(int argc, char** argv) {
         if (rc == LR_OK) rc = plan_run(&m, kind, &o, LR_NUTS_MAX_DEPTH, &pl);  // as every lr_run_* plans
         if (rc != LR_OK) std::printf("ERR %d %s\n", rc, g_err);
         else {
-            const InteriorPlan ip = plan_interior(&m, chains);
-            std::printf("%d %d %d %zu %d %lld %d %lld %d %d %d\n", pl.mode, pl.G, pl.R, pl.lds_bytes, ip.RS_i, (long long)ip.slice_len_i, ip.waves,
-                        (long long)pl.split, pl.G2, pl.R2, pl.mode2);
+            const StepwisePlan sp = plan_stepwise(&m, pl, kind, L, prec, chains);
+            if (stepwise)
+                std::printf("%d %lld %d %d %lld %d %d %d %d %d %d\n", sp.RS, (long long)sp.slice_len, sp.wide_engine, sp.RS_i, (long long)sp.slice_len_i, sp.waves,
+                            (int)sp.bf16_interior, (int)sp.path, sp.traj_tiles, sp.traj_fmt, (int)sp.alt_buffers);
+            else
+                std::printf("%d %d %d %zu %d %lld %d %lld %d %d %d\n", pl.mode, pl.G, pl.R, pl.lds_bytes, sp.RS_i, (long long)sp.slice_len_i, sp.waves,
+                            (long long)pl.split, pl.G2, pl.R2, pl.mode2);
         }
     }
     return 0;

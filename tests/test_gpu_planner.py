@@ -60,7 +60,7 @@ def test_float64_default_policy_is_within_ten_percent_of_the_best_alternative(C,
 @pytest.mark.parametrize("n,p,C", [(2000, 128, 1024), (3000, 128, 512), (4096, 128, 2048), (4096, 128, 3072), (3000, 64, 2048), (8000, 64, 512)])
 def test_wide_interior_engine_is_within_ten_percent_of_the_best_alternative(n, p, C, monkeypatch):
     """Wide models below one chain tile per CU: the engine's choice between the one-launch trajectory kernel (one chain tile per
-    workgroup) and the launch-per-step interior kernels (lr_engine.h: by chain count and image size, from tools/traj_rule_check.py's
+    workgroup) and the launch-per-step interior kernels (lr_plan.h plan_stepwise: by chain count and image size, from tools/traj_rule_check.py's
     measurements) against both forced alternatives -- us per evaluation of HMC L = 50 under the default policy, best of 3."""
     import ctypes as Ct
     import numpy as np

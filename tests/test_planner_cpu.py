@@ -14,6 +14,8 @@ from planner_cases import CASES, matches
 MODES = {0: "reg", 1: "lds", 2: "global", 3: "mfma", 4: "stepwise", 5: "mixed"}
 KIND = {"rwmh": 0, "mala": 1, "hmc": 2, "ul": 3}
 PREC = {"auto": 0, "full": 1, "bf16": 2}
+KIND["nuts"] = 4
+PATHS = ("EXACT", "PER_STEP", "FUSED", "TRAJ")  # lr_plan.h InteriorPath
 
 
 @pytest.fixture(scope="module")
@@ -48,7 +50,25 @@ def harness(tmp_path_factory):
                 plan["tail"] = {"from": int(f[7]), "mode": MODES[int(f[10])], "group": int(f[8]), "rows_per_lane": int(f[9])}
             res.append(plan)
         return res
+    def stepwise(requests, cus=256):
+        """requests: dicts of p, n, chains and, where not the default, dtype, kind, L, precision, fits_f16, wide_traj, wide_f16, tall_mx16, wide_waves
+        -> the StepwisePlan of each as a dict (lr_plan.h plan_stepwise)"""
+        dflt = dict(dtype=0, kind="hmc", L=50, precision="auto", fits_f16=1, wide_traj=-1, wide_f16=1, tall_mx16=1, wide_waves=0)
+        rq = [dict(dflt, **r) for r in requests]
+        text = "".join(f"{r['dtype']} {r['p']} {r['n']} {r['chains']} {KIND[r['kind']]} {r['L']} {PREC[r['precision']]} {r['fits_f16']} {r['wide_traj']} {r['wide_f16']} "
+                       f"{r['tall_mx16']} {r['wide_waves']} {cus}\n" for r in rq)
+        r = subprocess.run([exe, "stepwise"], input=text, capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.strip().split("\n")
+        assert len(lines) == len(rq) and not any(ln.startswith("ERR") for ln in lines), r.stdout[-2000:]
+        keys = ("RS", "slice_len", "wide_engine", "RS_i", "slice_len_i", "waves", "bf16_interior", "path", "traj_tiles", "traj_fmt", "alt_buffers")
+        plans = [dict(zip(keys, map(int, ln.split()))) for ln in lines]
+        for pl in plans:
+            pl["path"] = PATHS[pl["path"]]
+            pl["interior"] = (pl["RS_i"], pl["slice_len_i"], pl["waves"])
+        return plans
     ask.exe = exe
+    ask.stepwise = stepwise
     return ask
 
 
@@ -132,6 +152,81 @@ def test_interior_step_slicing_on_the_cpu(harness):
         rs, ln, wv = pl["interior"]
         if rs:
             assert rs * ln >= rq[2] and (rs - 1) * ln < rq[2] and ln % 32 == 0 and wv in (4, 8, 16), (rq, pl)
+
+
+# How HMC runs on the stepwise engine are launched (lr_plan.h plan_stepwise), float32, L = 50, 256 CUs, default options, rows that fit f16:
+# (p, n, chains, precision) -> path, and where stated the chain tiles per workgroup of the trajectory kernel, the operand format of the
+# wide interior kernels and the interior slicing.  The measured rule these follow is in the comments of plan_stepwise.
+STEPWISE_ROWS = [
+    (128, 2000, 1024, "auto", dict(path="TRAJ", traj_tiles=1, traj_fmt=2)),
+    (128, 3000, 1024, "auto", dict(path="TRAJ", traj_tiles=1)),
+    (128, 4096, 1024, "auto", dict(path="FUSED", interior=(4, 1024, 8))),
+    (128, 4096, 2048, "auto", dict(path="TRAJ", traj_tiles=1)),
+    (128, 4096, 3072, "auto", dict(path="TRAJ", traj_tiles=1)),
+    (128, 4096, 4096, "auto", dict(path="TRAJ", traj_tiles=1)),
+    (128, 4096, 8192, "auto", dict(path="TRAJ", traj_tiles=2, traj_fmt=2)),
+    (128, 4096, 8192, "bf16", dict(path="TRAJ", traj_tiles=2, traj_fmt=1)),
+    (128, 4096, 4096, "bf16", dict(path="TRAJ", traj_tiles=1, traj_fmt=2)),
+    (128, 4096, 1024, "full", dict(path="EXACT")), (128, 4096, 2048, "full", dict(path="EXACT")), (128, 4096, 8192, "full", dict(path="EXACT")),
+    (64, 3000, 1024, "auto", dict(path="TRAJ")),
+    (64, 5000, 1024, "auto", dict(path="FUSED", interior=(4, 1280, 8))),
+    (64, 8000, 2048, "auto", dict(path="FUSED", interior=(2, 4096, 8))),
+    (8, 100000, 1024, "auto", dict(path="FUSED", interior=(16, 6272, 16))),
+    (8, 100000, 4096, "auto", dict(path="PER_STEP", waves=4)),
+]
+
+
+def _rows(**over):
+    return [dict(p=p, n=n, chains=C, precision=prec, **over) for p, n, C, prec, _ in STEPWISE_ROWS]
+
+
+def test_stepwise_interior_path_on_the_cpu(harness):
+    plans = harness.stepwise(_rows())
+    bad = [(row[:4], pl) for row, pl in zip(STEPWISE_ROWS, plans) if any(pl[k] != v for k, v in row[4].items())]
+    assert not bad, bad
+    for row, pl in zip(STEPWISE_ROWS, plans):
+        assert pl["bf16_interior"] == (row[3] != "full") and pl["RS"] * pl["slice_len"] >= row[1] > (pl["RS"] - 1) * pl["slice_len"], (row, pl)
+        assert pl["wide_engine"] == (0 if row[0] <= 32 else 2 if row[2] >= 4096 else 1), (row, pl)
+    # every other family, lr_eval (L = 0) and NUTS evaluate exactly, whatever the precision asked for
+    others = [dict(p=p, n=n, chains=1024, kind=k, L=0, precision=prec) for p, n in ((128, 4096), (8, 100000)) for k in ("rwmh", "mala", "ul", "nuts")
+              for prec in ("auto", "bf16")]
+    assert all(pl["path"] == "EXACT" and not pl["bf16_interior"] for pl in harness.stepwise(others))
+    # float64 models take the same paths (their interior kernels read the float32 image)
+    f64 = harness.stepwise([dict(dtype=1, p=128, n=2000, chains=1024), dict(dtype=1, p=128, n=4096, chains=1024), dict(dtype=1, p=8, n=100000, chains=1024)])
+    assert [pl["path"] for pl in f64] == ["TRAJ", "FUSED", "FUSED"] and all(pl["wide_engine"] == 0 for pl in f64)
+
+
+def test_stepwise_debug_options_on_the_cpu(harness):
+    is_traj = [e["path"] == "TRAJ" for *_, e in STEPWISE_ROWS]
+    wide = [p > 32 and prec != "full" for p, _, _, prec, _ in STEPWISE_ROWS]
+    off = harness.stepwise(_rows(wide_traj=0))
+    assert all(pl["path"] in ("PER_STEP", "FUSED") for pl, t in zip(off, is_traj) if t)
+    assert all(pl["path"] == row[4]["path"] for pl, row, t in zip(off, STEPWISE_ROWS, is_traj) if not t)
+    for force in (1, 2):
+        forced = harness.stepwise(_rows(wide_traj=force))
+        assert all(pl["path"] == "TRAJ" and pl["traj_tiles"] == force for pl, w in zip(forced, wide) if w)
+        assert all(pl["path"] == row[4]["path"] for pl, row, w in zip(forced, STEPWISE_ROWS, wide) if not w)  # narrow models and full precision: unmoved
+    # without the f16 image: the bf16 pieces -- two of beta (0), or one (1) where LR_PREC_BF16 asks for it and the two-tile kernel runs anyway
+    one_piece = [int(prec == "bf16" and C > 16 * 256) for _, _, C, prec, _ in STEPWISE_ROWS]
+    assert [pl["traj_fmt"] for pl in harness.stepwise(_rows(wide_f16=0))] == one_piece == [pl["traj_fmt"] for pl in harness.stepwise(_rows(fits_f16=0))]
+    assert all(pl["traj_fmt"] == 2 for pl, w in zip(harness.stepwise(_rows(wide_f16=2)), wide) if w)  # f16 also where LR_PREC_BF16 would take one bf16 piece
+    tall = harness.stepwise([dict(p=8, n=100000, chains=1024, tall_mx16=0)])[0]
+    assert tall["waves"] == 4 and tall["path"] == "PER_STEP" and not tall["alt_buffers"]
+    assert [pl["wide_engine"] for pl in harness.stepwise([dict(p=128, n=4096, chains=C, wide_waves=w) for C in (1024, 8192) for w in (4, 8)])] == [1, 2, 1, 2]
+
+
+def test_stepwise_plan_invariants_on_the_cpu(harness):
+    """L = 1 has no interior step and never plans the trajectory kernel; the second buffer pair is planned exactly when there is an interior
+    slicing and the model is wide or the interior kernel is the 16-wave one -- over shapes, chain counts, precisions and options."""
+    sweep = [dict(p=p, n=n, chains=C, precision=prec, L=L, **opt) for p, n in ((128, 900), (128, 4096), (64, 5000), (100, 300), (8, 3000), (8, 100000), (20, 1500), (30, 5000))
+             for C in (70, 1024, 3072, 4096, 8192) for prec in ("auto", "full", "bf16") for L in (1, 2, 50)
+             for opt in ({}, {"wide_traj": 1}, {"wide_traj": 2}, {"tall_mx16": 0}, {"dtype": 1})]
+    for rq, pl in zip(sweep, harness.stepwise(sweep)):
+        assert rq["L"] > 1 or pl["path"] != "TRAJ", (rq, pl)
+        assert pl["alt_buffers"] == (pl["RS_i"] > 0 and (rq["p"] > 32 or pl["waves"] == 16)), (rq, pl)
+        assert (pl["path"] == "EXACT") == (not pl["bf16_interior"]) == (rq["precision"] == "full"), (rq, pl)
+        if pl["path"] == "FUSED":
+            assert pl["alt_buffers"] and pl["RS_i"] <= (4 if rq["p"] > 32 else 16), (rq, pl)
 
 
 def test_half_precision_image_rounding_and_range_rule(harness):
