@@ -23,6 +23,10 @@
  *                elpd_i  = log((S - n_t) + sum_j exp(log w_j - v_(j))) - log(sum_B exp(v_s) + sum_j w_j) - a
  *                n_eff_i = (sum w)^2 / sum w^2           lppd_i = log((1 / S) sum_s exp(l_s))
  *            (raw weights: the first bracket is S).  r_eff = 1: no correction for the autocorrelation of the draws.
+ *            A limit of n_eff as defined: both sums are plain float64, so where every smoothed weight lies below about 1e-162 the sum
+ *            of squares underflows to 0 and n_eff_i is 0 / 0 = NaN from a finite column, while elpd_i, khat_i and lppd_i stay finite.
+ *            It takes a fitted tail of tiny scale under a cutoff of exp(-thousands) -- log-likelihoods spread over thousands of nats,
+ *            khat far above 0.7, which flags the observation anyway (tests/test_predict_regimes_cpu.py reaches it).
  *
  * The table has LR_LOO_ROWS = 5 float64 rows of length n:  elpd_loo_i, khat_i, n_eff_i, lppd_i, n_tail_i.
  *
