@@ -20,7 +20,7 @@ from .data import load_pima, load_pima_parquet, synthetic_logreg  # noqa: F401
 from .diagnostics import describe, ess_geyer, ess_per_param, ess_pooled, split_rhat, summarise  # noqa: F401
 from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKernel, nutsKernel, pgKernel, rwProposal,  # noqa: F401
                       ulKernel)
-from .adapt import nuts_warmup, nuts_warmup_dense  # noqa: F401
+from .adapt import nuts_warmup, nuts_warmup_dense, nuts_warmup_stepwise  # noqa: F401
 from .model import DeviceArray, LogReg  # noqa: F401
 from .optimize import find_map, laplace_metric, overdispersed_init  # noqa: F401
 from .predict import PosteriorPredictive, merge_predictive, predict_proba, waic, waic_from_table  # noqa: F401
@@ -31,4 +31,4 @@ __all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "mala
            "rwProposal", "mcmc", "load_pima", "load_pima_parquet", "synthetic_logreg", "summarise", "describe",
            "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "laplace_metric", "overdispersed_init", "write_parquet",
            "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals", "Covariance", "covariance_scaling", "merge_covariance",
-           "nuts_warmup", "nuts_warmup_dense", "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare"]
+           "nuts_warmup", "nuts_warmup_dense", "nuts_warmup_stepwise", "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare"]

@@ -181,6 +181,13 @@ ADAPT_SYMBOLS = {
     "lr_adapt_destroy": (None, [_vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/logreg_hip_adapt_tall.h declares: the warm-up on the stepwise engine.  A table of its
+# own like ADAPT_SYMBOLS, bound on first use (load_adapt_tall); the handle is an lr_adapt, read and destroyed through ADAPT_SYMBOLS
+ADAPT_TALL_SYMBOLS = {
+    "lr_tall_adapt_create": ADAPT_SYMBOLS["lr_adapt_create"],
+    "lr_tall_adapt_run": ADAPT_SYMBOLS["lr_adapt_run"],
+}
+
 # name -> (restype, argtypes); every symbol include/logreg_hip_dense.h declares.  A table of its own like ADAPT_SYMBOLS, bound on first use
 # (load_dense)
 DENSE_SYMBOLS = {
@@ -217,6 +224,7 @@ _marg = None
 _loo = None
 _cov = None
 _adapt = None
+_adapt_tall = None
 
 
 def _bind(L, table, slot=None):
@@ -300,6 +308,17 @@ def bind_adapt(L):
 def load_adapt():
     """The library with the NUTS warm-up entry points bound (the same liblogreg_hip.so as load())."""
     return bind_adapt(load())
+
+
+def bind_adapt_tall(L):
+    """`L` (a loaded library handle) with the entry points of the NUTS warm-up on the stepwise engine bound, and those of the warm-up
+    itself, which serve its handle; resolved once per handle."""
+    return _bind(bind_adapt(L), ADAPT_TALL_SYMBOLS, "_adapt_tall")
+
+
+def load_adapt_tall():
+    """The library with the stepwise warm-up's entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_adapt_tall(load())
 
 
 def bind_dense(L):

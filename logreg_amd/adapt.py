@@ -10,6 +10,9 @@ Every iteration the mean acceptance statistic of all C chains drives one dual-av
 windows the states of all chains enter one pooled variance per coordinate: 4096 chains give both with almost no noise.  The W iterations
 are enqueued back to back, with no host round trip.  The result depends on the chain count: a shard of a larger run (`mcmc_sharded`)
 adapts by itself; pooling across ranks is not built.  There is no CPU path.
+
+Tall and wide models (rows beyond the LDS, or 32 < p <= 128) sample on the stepwise engine (`mcmc(..., mode="stepwise")`); their warm-up is
+`nuts_warmup_stepwise(...)` (include/logreg_hip_adapt_tall.h): the same adaptation, the iterations as that engine's launches.
 """
 from __future__ import annotations
 
@@ -43,6 +46,14 @@ def _adapt_library(L=None):
         raise _lib.LogregHipError(f"this library has no warm-up entry points (include/logreg_hip_adapt.h): {e}") from e
 
 
+def _adapt_tall_library(L=None):
+    L = _lib.load() if L is None else L
+    try:
+        return _lib.bind_adapt_tall(L)
+    except AttributeError as e:
+        raise _lib.LogregHipError(f"this library has no stepwise warm-up entry points (include/logreg_hip_adapt_tall.h): {e}") from e
+
+
 def _dense_library(L=None):
     L = _lib.load() if L is None else L
     try:
@@ -51,11 +62,11 @@ def _dense_library(L=None):
         raise _lib.LogregHipError(f"this library has no dense-metric entry points (include/logreg_hip_dense.h): {e}") from e
 
 
-def _warmup(who, symbols, library, start, shapes, finish, lpost, glp, init, num_warmup, target_accept, eps, max_depth, adapt_metric, seed, chain_offset,
+def _warmup(who, symbols, mode, library, start, shapes, finish, lpost, glp, init, num_warmup, target_accept, eps, max_depth, adapt_metric, seed, chain_offset,
             keep):
     """The body of `nuts_warmup` and `nuts_warmup_dense`: the checks, the start state and the seed, create / run / result / trace / destroy
-    and the result.  What differs comes as arguments: `who` names the caller in the error text, `symbols` is the prefix of the five entry
-    points in the binding `library`, `start(p)` checks the start metric and returns (`AdaptOpts.dmm0` or None, the further array
+    and the result.  What differs comes as arguments: `who` names the caller in the error text, `symbols` are the prefixes of the entry
+    points in the binding `library` (create and run; result, trace and destroy), `mode` is the launch mode of the run (`_lib.MODE_*`), `start(p)` checks the start metric and returns (`AdaptOpts.dmm0` or None, the further array
     arguments of create), `shapes(p)` the shapes of the metric and of a window's row of `metric_trace`, `finish(res, metric, max_depth)`
     adds the metric and the `kernel` to the result."""
     model = _model_of(lpost, "lpost")
@@ -77,27 +88,28 @@ def _warmup(who, symbols, library, start, shapes, finish, lpost, glp, init, num_
         raise ValueError(f"init must be [p] or [C,p] with p={p}; got {np.shape(init)}")
     Cn = st.shape[0]
     L = library(model._L)  # the library that made the model
+    make, read = symbols
     _lib.require_gpu()
     if seed is None:
         seed = int(np.random.randint(0, 2**31 - 1))
     seed = int(seed)
     o = AdaptOpts(W=W, adapt_metric=int(bool(adapt_metric)), delta=float(target_accept), eps0=float(eps), dmm0=None if dmm0 is None else dmm0.ctypes.data)
     h = C.c_void_p()
-    check(getattr(L, symbols + "_create")(model.handle, Cn, C.byref(o), *(a.ctypes.data for a in more), C.byref(h)))
+    check(getattr(L, make + "_create")(model.handle, Cn, C.byref(o), *(a.ctypes.data for a in more), C.byref(h)))
     try:
         counters = np.zeros(Cn, dtype=NUTS_COUNTERS)
         draws = np.empty((W, Cn, p), dtype=model.np_dtype) if keep else None
-        opts = RunOpts(n_chains=Cn, chain_offset=int(chain_offset), thin=1, iters=1, seed=seed & 0xFFFFFFFFFFFFFFFF, group=0, mode=_lib.MODE_AUTO, on_device=0)
-        check(getattr(L, symbols + "_run")(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
+        opts = RunOpts(n_chains=Cn, chain_offset=int(chain_offset), thin=1, iters=1, seed=seed & 0xFFFFFFFFFFFFFFFF, group=0, mode=mode, on_device=0)
+        check(getattr(L, make + "_run")(h, st.ctypes.data, W, max_depth, C.byref(opts), draws.ctypes.data if keep else None, counters.ctypes.data, None, None))
         e, info = C.c_double(), AdaptInfo()
         metric_shape, row_shape = shapes(p)
         metric = np.empty(metric_shape, dtype=np.float64)
-        check(getattr(L, symbols + "_result")(h, C.byref(e), metric.ctypes.data, C.byref(info)))
+        check(getattr(L, read + "_result")(h, C.byref(e), metric.ctypes.data, C.byref(info)))
         trace = np.zeros((W, _lib.ADAPT_TRACE_COLS), dtype=np.float64)
         metric_trace = np.zeros((info.n_windows, *row_shape), dtype=np.float64)
-        check(getattr(L, symbols + "_trace")(h, trace.ctypes.data, metric_trace.ctypes.data if info.n_windows else None))
+        check(getattr(L, read + "_trace")(h, trace.ctypes.data, metric_trace.ctypes.data if info.n_windows else None))
     finally:
-        getattr(L, symbols + "_destroy")(h)
+        getattr(L, read + "_destroy")(h)
     res = SimpleNamespace(eps=float(e.value), state=st.astype(np.float64), trace=trace, metric_trace=metric_trace,
                           info={"n_leapfrog": counters["n_leapfrog"].astype(np.int64), "divergent": counters["divergent"].astype(np.int64),
                                 "max_depth_hits": counters["max_depth_hits"].astype(np.int64), "mean_depth": counters["depth_sum"] / W,
@@ -109,14 +121,8 @@ def _warmup(who, symbols, library, start, shapes, finish, lpost, glp, init, num_
     return res
 
 
-def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
-                chain_offset=0, keep=False):
-    """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
-
-    Returns an object with `eps`, `dmm`, `pre` (= 1 / dmm: BlackJAX's inverse mass matrix), `state` `[C, p]`, `kernel`
-    (`nutsKernel(lpost, glp, eps, dmm, max_depth)`, ready for `mcmc`), `trace` `[W, 5]` (columns `TRACE_COLUMNS`), `metric_trace`
-    `[windows, 2, p]` (var, dmm per window), `info` (the per-chain counters as `ChainSet.nuts_info` gives them, and `metric_skipped`,
-    `windows`, `seed`) and, with `keep=True`, `draws` `[W, C, p]`.  `lpost` and `glp` must be the closures of one `LogReg`."""
+def _nuts_warmup(who, mode, lpost, glp, init, num_warmup, target_accept, eps, dmm, max_depth, adapt_metric, seed, chain_offset, keep):
+    """`nuts_warmup` (`mode` "auto") and `nuts_warmup_stepwise` ("stepwise"): the diagonal metric's start and finish; the engine as data"""
     def start(p):
         dmm0 = np.ascontiguousarray(np.broadcast_to(np.asarray(dmm, dtype=np.float64), (p,)))
         if not np.all(np.isfinite(dmm0) & (dmm0 > 0)):
@@ -125,8 +131,30 @@ def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0
 
     def finish(res, dm, depth):
         res.dmm, res.pre, res.kernel = dm, 1.0 / dm, nutsKernel(lpost, glp, res.eps, dm, depth)
-    return _warmup("nuts_warmup", "lr_adapt", _adapt_library, start, lambda p: ((p,), (2, p)), finish, lpost, glp, init, num_warmup, target_accept, eps,
-                   max_depth, adapt_metric, seed, chain_offset, keep)
+    tall = mode == "stepwise"
+    return _warmup(who, ("lr_tall_adapt" if tall else "lr_adapt", "lr_adapt"), _lib.MODE_BY_NAME[mode], _adapt_tall_library if tall else _adapt_library, start,
+                   lambda p: ((p,), (2, p)), finish, lpost, glp, init, num_warmup, target_accept, eps, max_depth, adapt_metric, seed, chain_offset, keep)
+
+
+def nuts_warmup(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
+                chain_offset=0, keep=False):
+    """Run `num_warmup` adaptation iterations of all chains of `init` (`[p]` or `[C, p]`) and return the adapted sampler.
+
+    Returns an object with `eps`, `dmm`, `pre` (= 1 / dmm: BlackJAX's inverse mass matrix), `state` `[C, p]`, `kernel`
+    (`nutsKernel(lpost, glp, eps, dmm, max_depth)`, ready for `mcmc`), `trace` `[W, 5]` (columns `TRACE_COLUMNS`), `metric_trace`
+    `[windows, 2, p]` (var, dmm per window), `info` (the per-chain counters as `ChainSet.nuts_info` gives them, and `metric_skipped`,
+    `windows`, `seed`) and, with `keep=True`, `draws` `[W, C, p]`.  `lpost` and `glp` must be the closures of one `LogReg`."""
+    return _nuts_warmup("nuts_warmup", "auto", lpost, glp, init, num_warmup, target_accept, eps, dmm, max_depth, adapt_metric, seed, chain_offset, keep)
+
+
+def nuts_warmup_stepwise(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, dmm=1, max_depth=10, adapt_metric=True, seed=None,
+                         chain_offset=0, keep=False):
+    """`nuts_warmup` on the stepwise engine (include/logreg_hip_adapt_tall.h), for the models `mcmc(..., mode="stepwise")` samples -- 32 < p
+    <= 128, or rows beyond the LDS -- and only for those (a shape of the fused kernel is refused, with the hint to `nuts_warmup`).  The
+    same arguments, the same result; run it with `mcmc(res.state, res.kernel, mode="stepwise")`.  The host waits on the device at the end of
+    every tree doubling, as that sampling run does.  A function of its own, as `nuts_warmup_dense` is: `nuts_warmup`'s parameter list is
+    pinned by its tests."""
+    return _nuts_warmup("nuts_warmup_stepwise", "stepwise", lpost, glp, init, num_warmup, target_accept, eps, dmm, max_depth, adapt_metric, seed, chain_offset, keep)
 
 
 def nuts_warmup_dense(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, eps=1.0, inv_metric=None, max_depth=10, adapt_metric=True, seed=None,
@@ -147,5 +175,5 @@ def nuts_warmup_dense(lpost, glp, init, num_warmup=1000, *, target_accept=0.8, e
 
     def finish(res, sig, depth):
         res.inv_metric, res.kernel = sig, nutsKernel(lpost, glp, res.eps, max_depth=depth, inv_metric=sig)
-    return _warmup("nuts_warmup_dense", "lr_dense_adapt", _dense_library, start, lambda p: ((p, p), (p, p)), finish, lpost, glp, init, num_warmup, target_accept,
+    return _warmup("nuts_warmup_dense", ("lr_dense_adapt", "lr_dense_adapt"), _lib.MODE_AUTO, _dense_library, start, lambda p: ((p, p), (p, p)), finish, lpost, glp, init, num_warmup, target_accept,
                    eps, max_depth, adapt_metric, seed, chain_offset, keep)

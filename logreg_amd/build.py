@@ -79,6 +79,7 @@ def _sources():
                                                                         os.path.join(INCLUDE, "logreg_hip_loo.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_cov.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_adapt.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_adapt_tall.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_dense.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_pg.h")]
 

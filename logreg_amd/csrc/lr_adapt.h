@@ -2,10 +2,12 @@
 // (include/logreg_hip_adapt.h states the arithmetic line by line; this file is that text as code).  Per iteration, on one stream:
 //     k_nuts<.., TUNED>   one NUTS iteration from the device-resident NutsTune block; writes astat [C]        (lr_nuts.h)
 //     k_adapt_partial     one workgroup per 256 chains: sum256 of astat and, in a metric window, (n, mean, M2) per coordinate
-//     k_adapt_update      one wave: merges the partials in workgroup order, the dual-averaging step, the fold into the window's triple,
+//     k_adapt_update      one wave (P = 128: two): merges the partials in workgroup order, the dual-averaging step, the fold into the window's triple,
 //                         at a window's end the metric and the restart; writes the next NutsTune block, a trace row, a metric row
 // The schedule is known on the host: the iteration index, m and the window flags come in by value (AdaptStep).  Everything is float64,
 // nothing contracts (products inside sums are spelled fma), no float atomics; the partials are plain stores in workgroup order.
+// On the stepwise engine (include/logreg_hip_adapt_tall.h) the iteration is the launches of k_tall_nuts_update<.., TUNED> (lr_tall_nuts.h) and
+// the two kernels run at P = 64 and 128 as well, over the engine's padded states (row stride `ld` = P).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,11 +49,14 @@ __device__ __forceinline__ void adapt_merge(double& na, double& ma, double& Ma, 
     na = n;
 }
 
+// The two kernels' bodies.  Each has two names: k_adapt_* at the fused kernels' widths (P <= 32, both engines) and k_tall_adapt_* at the
+// wide ones (P = 64, 128: the stepwise engine only), so that what is instantiated per family can be counted by name.
 template <typename T, int P>
-__global__ void __launch_bounds__(kAdaptBlock) k_adapt_partial(const T* __restrict__ x, const double* __restrict__ astat, int64_t C, int p, int in_window,
-                                                                double* __restrict__ partial) {
+__device__ __forceinline__ void adapt_partial(const T* __restrict__ x, int64_t ld, const double* __restrict__ astat, int64_t C, int p, int in_window,
+                                              double* __restrict__ partial) {
+    // x: the states, row c at x + c ld (ld = p: the caller's [C][p]; ld = P: the stepwise engine's workspace)
 #pragma clang fp contract(off)
-    static_assert(P >= 4 && P <= 32 && kAdaptBlock % P == 0, "lane map");
+    static_assert(P >= 4 && P <= 128 && kAdaptBlock % P == 0, "lane map");
     constexpr int Q = kAdaptBlock / P;
     __shared__ double v[kAdaptBlock];
     const int tid = threadIdx.x;
@@ -74,7 +79,7 @@ __global__ void __launch_bounds__(kAdaptBlock) k_adapt_partial(const T* __restri
     const bool real = j < p;
     double s1 = 0.0;
     if (real)
-        for (int i = q; i < nb; i += Q) s1 += (double)x[(c0 + i) * p + j];
+        for (int i = q; i < nb; i += Q) s1 += (double)x[(c0 + i) * ld + j];
     v[tid] = s1;
     __syncthreads();
     for (int s = Q / 2; s > 0; s >>= 1) {
@@ -86,7 +91,7 @@ __global__ void __launch_bounds__(kAdaptBlock) k_adapt_partial(const T* __restri
     double s2 = 0.0;
     if (real)
         for (int i = q; i < nb; i += Q) {
-            const double d = (double)x[(c0 + i) * p + j] - mean;
+            const double d = (double)x[(c0 + i) * ld + j] - mean;
             s2 = __builtin_fma(d, d, s2);
         }
     v[tid] = s2;
@@ -100,9 +105,24 @@ __global__ void __launch_bounds__(kAdaptBlock) k_adapt_partial(const T* __restri
         out[2 + P + tid] = v[tid];
     }
 }
-
 template <typename T, int P>
-__global__ void __launch_bounds__(64) k_adapt_update(AdaptDev d, AdaptStep s, NutsTune<T, P>* __restrict__ tune) {
+__global__ void __launch_bounds__(kAdaptBlock) k_adapt_partial(const T* __restrict__ x, int64_t ld, const double* __restrict__ astat, int64_t C, int p,
+                                                                int in_window, double* __restrict__ partial) {
+    static_assert(P <= 32, "the wide widths: k_tall_adapt_partial");
+    adapt_partial<T, P>(x, ld, astat, C, p, in_window, partial);
+}
+template <typename T, int P>
+__global__ void __launch_bounds__(kAdaptBlock) k_tall_adapt_partial(const T* __restrict__ x, int64_t ld, const double* __restrict__ astat, int64_t C, int p,
+                                                                     int in_window, double* __restrict__ partial) {
+    static_assert(P > 32, "the fused kernels' widths: k_adapt_partial");
+    adapt_partial<T, P>(x, ld, astat, C, p, in_window, partial);
+}
+
+// lane = coordinate: one wave, two at P = 128.  What a lane reads that lane 0 writes (d.win[0]) it reads ahead of the one
+// __syncthreads(), and lane 0 writes behind it; what lane 0 reads of the others (sh_skip) it reads behind it: the order holds across waves.
+__host__ __device__ constexpr int adapt_update_lanes(int P) { return P > 64 ? P : 64; }
+template <typename T, int P>
+__device__ __forceinline__ void adapt_update(const AdaptDev& d, const AdaptStep& s, NutsTune<T, P>* __restrict__ tune) {
 #pragma clang fp contract(off)
     constexpr int PW = adapt_partial_words(P);
     __shared__ double sh_eps;
@@ -185,6 +205,16 @@ __global__ void __launch_bounds__(64) k_adapt_update(AdaptDev d, AdaptStep s, Nu
         tune->b[j] = mine ? (T)(eps / dm) : T(0);
         tune->c[j] = mine ? (T)(1.0 / dm) : T(0);
     }
+}
+template <typename T, int P>
+__global__ void __launch_bounds__(adapt_update_lanes(P)) k_adapt_update(AdaptDev d, AdaptStep s, NutsTune<T, P>* __restrict__ tune) {
+    static_assert(P <= 32, "the wide widths: k_tall_adapt_update");
+    adapt_update<T, P>(d, s, tune);
+}
+template <typename T, int P>
+__global__ void __launch_bounds__(adapt_update_lanes(P)) k_tall_adapt_update(AdaptDev d, AdaptStep s, NutsTune<T, P>* __restrict__ tune) {
+    static_assert(P > 32, "the fused kernels' widths: k_adapt_update");
+    adapt_update<T, P>(d, s, tune);
 }
 
 }  // namespace lr

@@ -20,6 +20,7 @@
 #include "../../include/logreg_hip_loo.h"
 #include "../../include/logreg_hip_cov.h"
 #include "../../include/logreg_hip_adapt.h"
+#include "../../include/logreg_hip_adapt_tall.h"
 #include "../../include/logreg_hip_dense.h"
 #include "../../include/logreg_hip_pg.h"
 
@@ -32,7 +33,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "lr_inst.h"
@@ -1469,6 +1472,7 @@ struct lr_adapt {
     int window = 0;    // the first window that has not ended
     hipStream_t last = nullptr;  // stream of the last run call: results follow it
     bool failed = false;         // a launch failed part-way through a run call: what is enqueued no longer matches the counts above
+    bool tall = false;           // lr_tall_adapt_create: the iterations run on the stepwise engine (include/logreg_hip_adapt_tall.h)
     // one device block: da | dmm [p] | window triple [1 + 2 p] | partials [B][2 + 2 P] | trace [W][5] | metric [windows][2][p] | astat [C] | NutsTune
     double* d_fixed = nullptr;
     size_t words = 0, tune_bytes = 0;
@@ -1522,8 +1526,38 @@ int tune_start(int p, double eps, const double* dmm, std::vector<unsigned char>*
     return LR_OK;
 }
 int tune_start_any(const lr_model* m, double eps, const double* dmm, std::vector<unsigned char>* img) {
-    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, tune_start, m->p, eps, dmm, img)
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, tune_start, m->p, eps, dmm, img)
     return bad_width(m);
+}
+
+// What follows iteration h->t's NUTS launches on `st`: the pooled partials of `astat` [C] and of the states x [C][ld], the update of the tuning
+// block, and the handle's count of where the schedule stands; the handle's dense part adds its co-moments inside a window and its window end.
+template <typename T, int P>
+int adapt_after(lr_adapt* h, hipStream_t st, const void* x, int64_t ld, const double* astat) {
+    lr_model* m = h->m;
+    DenseAdapt* dense = h->dense.get();
+    const lr::AdaptDev dev = h->dev();
+    const bool in_window = h->window < h->n_windows && h->t >= (h->window ? h->ends[h->window - 1] : h->init);
+    const bool window_end = in_window && h->t == h->ends[h->window] - 1;
+    const auto xs = static_cast<const T*>(x);
+    if constexpr (P <= 32) hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, xs, ld, astat, h->C, m->p, in_window ? 1 : 0, dev.partial);
+    else hipLaunchKernelGGL((lr::k_tall_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, xs, ld, astat, h->C, m->p, in_window ? 1 : 0, dev.partial);
+    LR_HIP(hipGetLastError());
+    if constexpr (P <= 32) {  // (the dense metric: the fused kernels' widths, states [C][p])
+        if (dense && in_window)
+            if (const int rc = dense->accumulate<T, P>(st, const_cast<void*>(x), h->C, h->B, m->p)) return rc;
+    }
+    const lr::AdaptStep s{h->C, h->t, m->p, h->m_since + 1, in_window ? h->window : -1, window_end ? 1 : 0, h->t == h->W - 1 ? 1 : 0, h->delta, h->gamma, h->t0, h->kappa};
+    auto* tune = static_cast<lr::NutsTune<T, P>*>(h->tune());
+    if constexpr (P <= 32) hipLaunchKernelGGL((lr::k_adapt_update<T, P>), dim3(1), dim3(lr::adapt_update_lanes(P)), 0, st, dev, s, tune);
+    else hipLaunchKernelGGL((lr::k_tall_adapt_update<T, P>), dim3(1), dim3(lr::adapt_update_lanes(P)), 0, st, dev, s, tune);
+    LR_HIP(hipGetLastError());
+    ++h->t;
+    h->m_since = window_end ? 0 : h->m_since + 1;
+    if (window_end) ++h->window;
+    if (dense && window_end)
+        if (const int rc = dense->window_end(m, st)) return rc;
+    return LR_OK;
 }
 
 // `iters` iterations on `st`: the tuned NUTS launch, the pooled partials, the update; the handle's dense part adds its co-moments inside a
@@ -1533,7 +1567,6 @@ int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts
                   int8_t* depth_out, double* astat_out, int64_t iters) {
     lr_model* m = h->m;
     DenseAdapt* dense = h->dense.get();
-    const lr::AdaptDev dev = h->dev();
     auto* tune = static_cast<lr::NutsTune<T, P>*>(h->tune());
     const size_t row = (size_t)h->C * m->p;
     h->last = st;
@@ -1544,26 +1577,31 @@ int adapt_enqueue(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts
         const RunArrays d{state, nullptr, out ? static_cast<T*>(out) + (size_t)i * row : nullptr, counters, sizeof(lr_nuts_counters),
                           depth_out ? depth_out + (size_t)i * h->C : nullptr};
         if (const int rc = nuts_launch<T, P>(m, pl, st, &it, 0.0, max_depth, mt, d)) return rc;
-        const bool in_window = h->window < h->n_windows && h->t >= (h->window ? h->ends[h->window - 1] : h->init);
-        const bool window_end = in_window && h->t == h->ends[h->window] - 1;
-        hipLaunchKernelGGL((lr::k_adapt_partial<T, P>), dim3((unsigned)h->B), dim3(lr::kAdaptBlock), 0, st, static_cast<const T*>(state), mt.astat, h->C, m->p, in_window ? 1 : 0,
-                           dev.partial);
-        LR_HIP(hipGetLastError());
-        if (dense && in_window)
-            if (const int rc = dense->accumulate<T, P>(st, state, h->C, h->B, m->p)) return rc;
-        const lr::AdaptStep s{h->C, h->t, m->p, h->m_since + 1, in_window ? h->window : -1, window_end ? 1 : 0, h->t == h->W - 1 ? 1 : 0, h->delta, h->gamma, h->t0, h->kappa};
-        hipLaunchKernelGGL((lr::k_adapt_update<T, P>), dim3(1), dim3(64), 0, st, dev, s, tune);
-        LR_HIP(hipGetLastError());
-        ++h->t;
-        h->m_since = window_end ? 0 : h->m_since + 1;
-        if (window_end) ++h->window;
-        if (dense && window_end)
-            if (const int rc = dense->window_end(m, st)) return rc;
+        if (const int rc = adapt_after<T, P>(h, st, state, m->p, mt.astat)) return rc;
     }
     return LR_OK;
 }
+// ... and on the stepwise engine (include/logreg_hip_adapt_tall.h): ONE pass of the engine's NUTS loop over the call's iterations, the chains
+// resident in its workspace, with adapt_after behind every iteration's end
+template <typename T, int P>
+int adapt_enqueue_tall(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
+                       int8_t* depth_out, double* astat_out, int64_t iters) {
+    h->last = st;
+    lr_run_opts oo = *o;
+    oo.iters = iters;
+    oo.iter_offset = LR_ADAPT_ITER_BASE + h->t;
+    RunSpec rs{};  // (the tuning is the handle's block)
+    rs.kind = lr::KIND_HMC;
+    const NutsWarm warm{h->tune(), [&](int64_t i) { return astat_out ? astat_out + (size_t)i * h->C : h->astat(); },
+                        [&](int64_t, const void* x, int64_t ld, const double* astat) { return adapt_after<T, P>(h, st, x, ld, astat); }};
+    return do_nuts_stepwise_t<T, P>(h->m, pl, st, rs, &oo, max_depth, state, out, counters, depth_out, &warm);
+}
 int adapt_enqueue_any(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
                       int8_t* depth_out, double* astat_out, int64_t iters) {
+    if (h->tall) {
+        LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, h->m->dtype, h->m->P, adapt_enqueue_tall, h, pl, st, o, max_depth, state, out, counters, depth_out, astat_out, iters)
+        return bad_width(h->m);
+    }
     LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, h->m->dtype, h->m->P, adapt_enqueue, h, pl, st, o, max_depth, state, out, counters, depth_out, astat_out, iters)
     return bad_width(h->m);
 }
@@ -1572,7 +1610,8 @@ int adapt_enqueue_any(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_
 int adapt_enqueue_checked(lr_adapt* h, const Plan& pl, hipStream_t st, const lr_run_opts* o, int max_depth, void* state, void* out, lr_nuts_counters* counters,
                           int8_t* depth_out, double* astat_out, int64_t iters) {
     const int rc = adapt_enqueue_any(h, pl, st, o, max_depth, state, out, counters, depth_out, astat_out, iters);
-    if (rc != LR_OK) h->failed = true;
+    // (the stepwise engine's workspace is allocated before anything is enqueued: out of memory there leaves the handle as it was)
+    if (rc != LR_OK && !(h->tall && rc == LR_ERR_NOMEM)) h->failed = true;
     return rc;
 }
 
@@ -1612,24 +1651,32 @@ int lr_adapt_schedule(int32_t W, int32_t init_buffer, int32_t term_buffer, int32
     return LR_OK;
 }
 
-int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** out) {
-    if (!m || !o || !out) return fail(LR_ERR_INVALID, "lr_adapt_create: model / opts / out is NULL");
-    if (C <= 0) return fail(LR_ERR_INVALID, "lr_adapt_create: C must be positive (got %lld)", (long long)C);
-    if (C > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_adapt_create: %lld chains are beyond the launch grid", (long long)C);
-    if (o->W < 1) return fail(LR_ERR_INVALID, "lr_adapt_create: W must be >= 1 (got %d)", o->W);
+namespace {
+// lr_adapt_create and lr_tall_adapt_create (`tall`: on the stepwise engine, include/logreg_hip_adapt_tall.h): one set of argument checks, then
+// the shapes each takes
+int adapt_create(const char* who, bool tall, lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** out) {
+    if (!m || !o || !out) return fail(LR_ERR_INVALID, "%s: model / opts / out is NULL", who);
+    if (C <= 0) return fail(LR_ERR_INVALID, "%s: C must be positive (got %lld)", who, (long long)C);
+    if (C > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "%s: %lld chains are beyond the launch grid", who, (long long)C);
+    if (o->W < 1) return fail(LR_ERR_INVALID, "%s: W must be >= 1 (got %d)", who, o->W);
     if (o->init_buffer < 0 || o->term_buffer < 0 || o->base_window < 0)
-        return fail(LR_ERR_INVALID, "lr_adapt_create: the buffers must be >= 0, 0 for the default (got %d, %d, %d)", o->init_buffer, o->term_buffer, o->base_window);
-    if (!(o->delta >= 0 && o->delta < 1)) return fail(LR_ERR_INVALID, "lr_adapt_create: delta must be in (0, 1), 0 for the default 0.8 (got %g)", o->delta);
-    if (!(o->eps0 >= 0) || !std::isfinite(o->eps0)) return fail(LR_ERR_INVALID, "lr_adapt_create: eps0 must be finite and > 0, 0 for the default 1 (got %g)", o->eps0);
+        return fail(LR_ERR_INVALID, "%s: the buffers must be >= 0, 0 for the default (got %d, %d, %d)", who, o->init_buffer, o->term_buffer, o->base_window);
+    if (!(o->delta >= 0 && o->delta < 1)) return fail(LR_ERR_INVALID, "%s: delta must be in (0, 1), 0 for the default 0.8 (got %g)", who, o->delta);
+    if (!(o->eps0 >= 0) || !std::isfinite(o->eps0)) return fail(LR_ERR_INVALID, "%s: eps0 must be finite and > 0, 0 for the default 1 (got %g)", who, o->eps0);
     for (const double v : {o->gamma, o->t0, o->kappa})
-        if (!(v >= 0) || !std::isfinite(v)) return fail(LR_ERR_INVALID, "lr_adapt_create: gamma, t0 and kappa must be finite and > 0, 0 for the defaults (got %g)", v);
+        if (!(v >= 0) || !std::isfinite(v)) return fail(LR_ERR_INVALID, "%s: gamma, t0 and kappa must be finite and > 0, 0 for the defaults (got %g)", who, v);
     if (o->dmm0)
-        if (const int rc = positive_vec("lr_adapt_create: dmm0", o->dmm0, m->p)) return rc;
-    if (m->P > 32 || !m->table || !m->table->launch_nuts)
+        if (const int rc = positive_vec((std::string(who) + ": dmm0").c_str(), o->dmm0, m->p)) return rc;
+    if (!tall && (m->P > 32 || !m->table || !m->table->launch_nuts))
         return fail(LR_ERR_UNSUPPORTED, "NUTS: p = %d > 32 -- wide models run on the stepwise engine, which has no NUTS kernel", m->p);
-    if (const int rc = use_device(m->device, "lr_adapt_create")) return rc;
+    if (tall && nuts_fused_takes(m))
+        return fail(LR_ERR_UNSUPPORTED, "%s: the stepwise (tall-data) engine takes the NUTS warm-up only where the fused kernel cannot (p > 32, or rows beyond the "
+                    "LDS); here (n = %lld, p = %d) the warm-up is lr_adapt_create's, with the rows in LDS", who, (long long)m->n, m->p);
+    if (tall && (!m->table || !m->table->launch_tall_nuts_tuned)) return fail(LR_ERR_UNSUPPORTED, "%s: no stepwise NUTS kernel for padded p = %d", who, m->P);
+    if (const int rc = use_device(m->device, who)) return rc;
     std::unique_ptr<lr_adapt> h(new lr_adapt());
     h->m = m;
+    h->tall = tall;
     h->C = C;
     h->B = (C + lr::kAdaptBlock - 1) / lr::kAdaptBlock;
     h->W = o->W;
@@ -1647,7 +1694,7 @@ int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** o
     h->tune_bytes = tune.size();
     h->words = h->o_tune();
     const size_t want = h->words * sizeof(double) + h->tune_bytes;
-    if (hipMalloc((void**)&h->d_fixed, want) != hipSuccess) return fail(LR_ERR_NOMEM, "lr_adapt_create: allocating %zu bytes of state failed", want);
+    if (hipMalloc((void**)&h->d_fixed, want) != hipSuccess) return fail(LR_ERR_NOMEM, "%s: allocating %zu bytes of state failed", who, want);
     std::vector<double> img(h->words, 0.0);
     img[lr::AD_MU] = std::log(10.0 * eps0);
     img[lr::AD_EPS] = img[lr::AD_EPS_REPORT] = eps0;
@@ -1656,21 +1703,22 @@ int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** o
     if (e == hipSuccess) e = hipMemcpy(h->tune(), tune.data(), tune.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         lr_adapt_destroy(h.release());
-        return fail(LR_ERR_HIP, "lr_adapt_create: copying the start state failed: %s", hipGetErrorString(e));
+        return fail(LR_ERR_HIP, "%s: copying the start state failed: %s", who, hipGetErrorString(e));
     }
     *out = h.release();
     return LR_OK;
 }
 
-int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters, int8_t* depth_out,
-                 double* astat_out) {
-    if (!h || !state || !o) return fail(LR_ERR_INVALID, "lr_adapt_run: handle / state / opts is NULL");
-    if (h->failed) return fail(LR_ERR_HIP, "lr_adapt_run: a launch of an earlier call failed; this warm-up cannot go on (destroy the handle and start again)");
+// lr_adapt_run and lr_tall_adapt_run: one front; the handle says which engine runs the iterations, and the plan is that engine's
+int adapt_run(const char* who, lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters, int8_t* depth_out,
+              double* astat_out) {
+    if (!h || !state || !o) return fail(LR_ERR_INVALID, "%s: handle / state / opts is NULL", who);
+    if (h->failed) return fail(LR_ERR_HIP, "%s: a launch of an earlier call failed; this warm-up cannot go on (destroy the handle and start again)", who);
     if (iters < 0 || iters > h->W - h->t)
-        return fail(LR_ERR_INVALID, "lr_adapt_run: iters must be in 0..%lld, the iterations that remain of W = %d (got %lld)", (long long)(h->W - h->t), h->W, (long long)iters);
-    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "lr_adapt_run: max_depth must be in 1..%d (got %d)", LR_NUTS_MAX_DEPTH, max_depth);
-    if (o->n_chains != h->C) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->n_chains must be the handle's %lld chains (got %lld)", (long long)h->C, (long long)o->n_chains);
-    if (o->stats) return fail(LR_ERR_INVALID, "lr_adapt_run: opts->stats must be NULL (a warm-up keeps no streaming statistics)");
+        return fail(LR_ERR_INVALID, "%s: iters must be in 0..%lld, the iterations that remain of W = %d (got %lld)", who, (long long)(h->W - h->t), h->W, (long long)iters);
+    if (max_depth < 1 || max_depth > LR_NUTS_MAX_DEPTH) return fail(LR_ERR_INVALID, "%s: max_depth must be in 1..%d (got %d)", who, LR_NUTS_MAX_DEPTH, max_depth);
+    if (o->n_chains != h->C) return fail(LR_ERR_INVALID, "%s: opts->n_chains must be the handle's %lld chains (got %lld)", who, (long long)h->C, (long long)o->n_chains);
+    if (o->stats) return fail(LR_ERR_INVALID, "%s: opts->stats must be NULL (a warm-up keeps no streaming statistics)", who);
     lr_run_opts oo = *o;  // iters, thin and iter_offset are the warm-up's own (adapt_enqueue), the fields of the absent statistics as its launches have them
     oo.iters = 1;
     oo.thin = 1;
@@ -1679,9 +1727,11 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
     oo.stats_first = 0;
     lr_model* m = h->m;
     if (const int rc = check_opts(m, &oo, true)) return rc;
+    if (h->tall && oo.mode != LR_MODE_STEPWISE)
+        return fail(LR_ERR_UNSUPPORTED, "%s: opts->mode must be LR_MODE_STEPWISE (got %d): the handle's iterations run on the stepwise engine", who, oo.mode);
     LR_HIP(hipSetDevice(m->device));
     Plan pl;
-    if (const int rc = plan_nuts(m, oo.group, oo.mode, max_depth, &pl, h->dense != nullptr)) return rc;
+    if (const int rc = h->tall ? plan_nuts_stepwise(m, &oo, &pl) : plan_nuts(m, oo.group, oo.mode, max_depth, &pl, h->dense != nullptr)) return rc;
     if (iters == 0) return LR_OK;
     if (oo.on_device) return adapt_enqueue_checked(h, pl, (hipStream_t)oo.stream, &oo, max_depth, state, out, counters, depth_out, astat_out, iters);
     const size_t C = (size_t)h->C, sbytes = C * m->p * m->esize();
@@ -1693,7 +1743,7 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
         {&h->st_astat, astat_out, (size_t)iters * C * sizeof(double), false, "staged acceptance statistics"}};
     for (const auto& q : b)
         if (q.host)
-            if (const int rc = q.ws->grow(q.bytes, "lr_adapt_run", q.what)) return rc;
+            if (const int rc = q.ws->grow(q.bytes, who, q.what)) return rc;
     for (const auto& q : b)
         if (q.host && q.in) LR_HIP(hipMemcpy(q.ws->p, q.host, q.bytes, hipMemcpyHostToDevice));
     auto dp = [&](int i) { return b[i].host ? b[i].ws->p : nullptr; };
@@ -1704,6 +1754,25 @@ int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, con
     for (const auto& q : b)
         if (q.host) LR_HIP(hipMemcpy(q.host, q.ws->p, q.bytes, hipMemcpyDeviceToHost));
     return LR_OK;
+}
+
+}  // namespace
+
+int lr_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** out) { return adapt_create("lr_adapt_create", false, m, C, o, out); }
+
+int lr_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters, int8_t* depth_out,
+                 double* astat_out) {
+    if (h && h->tall) return fail(LR_ERR_INVALID, "lr_adapt_run: the handle is one of lr_tall_adapt_create (lr_tall_adapt_run advances it)");
+    return adapt_run("lr_adapt_run", h, state, iters, max_depth, o, out, counters, depth_out, astat_out);
+}
+
+// the warm-up on the stepwise engine (include/logreg_hip_adapt_tall.h): an lr_adapt whose iterations are the launches of lr_tall_nuts.h
+int lr_tall_adapt_create(lr_model* m, int64_t C, const lr_adapt_opts* o, lr_adapt** out) { return adapt_create("lr_tall_adapt_create", true, m, C, o, out); }
+
+int lr_tall_adapt_run(lr_adapt* h, void* state, int64_t iters, int32_t max_depth, const lr_run_opts* o, void* out, lr_nuts_counters* counters, int8_t* depth_out,
+                      double* astat_out) {
+    if (h && !h->tall) return fail(LR_ERR_INVALID, "lr_tall_adapt_run: the handle is not one of lr_tall_adapt_create");
+    return adapt_run("lr_tall_adapt_run", h, state, iters, max_depth, o, out, counters, depth_out, astat_out);
 }
 
 int lr_adapt_result(lr_adapt* h, double* eps, double* dmm, lr_adapt_info* info) { return adapt_result(h, nullptr, eps, dmm, info); }

@@ -325,12 +325,21 @@ int do_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs
 // a doubling on the caller's stream (at most max_depth - 1 waits per iteration); zero ends the iteration.  The loop is bounded by
 // 2^max_depth - 1 leaves whatever it reads, and a finished chain is inert, so the results do not depend on when the host looks.
 // Full precision at every leaf: the plan of a NUTS run is PATH_EXACT.
+//
+// A warm-up (NutsWarm; include/logreg_hip_adapt_tall.h) is the same loop on the TUNED kernel: the tuning comes from `tune`, every
+// iteration ends with flag = 0 and writes its acceptance statistics, `after` enqueues what rewrites the tuning block, and the next
+// iteration begins from the carried state as a launch of its own (NPH_CARRY), which reads the new tuning.
+struct NutsWarm {
+    const void* tune;  // NutsTune<T, P> in device memory
+    std::function<double*(int64_t)> astat;  // [C] of the call's iteration i
+    std::function<int(int64_t, const void* x, int64_t ld, const double* astat)> after;  // behind iteration i's end; x: the states [C][ld]
+};
 template <typename T, int P>
 int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, int max_depth, void* state, void* out,
-                       void* counters, int8_t* depth_out) {
+                       void* counters, int8_t* depth_out, const NutsWarm* warm) {
     const int64_t C = o->n_chains;
     const lr::InstTable* t = m->table;
-    if (!t->launch_tall_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
+    if (!t->launch_tall_nuts || !t->launch_tall_nuts_tuned) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
     const lr::NutsTallCarve cv = lr::nuts_tall_carve(C, P, sizeof(T), max_depth);
     lr::TallArgs<T, P> a;
     unsigned char* w = nullptr;
@@ -340,8 +349,12 @@ int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpe
     TallRun<T, P> run{t, st, a};
     const lr::NutsTallArgs<T> na{reinterpret_cast<T*>(w + cv.vec_off), reinterpret_cast<lr::NutsTallChain*>(w + cv.chain_off), reinterpret_cast<uint32_t*>(w + cv.tally_off),
                                  static_cast<lr::NutsCounters*>(counters), depth_out, max_depth};
+    lr::NutsTallTunedArgs<T, P> nt{na, warm ? static_cast<const lr::NutsTune<T, P>*>(warm->tune) : nullptr, nullptr};
     auto N = [&](int phase, int64_t iter, const lr::NutsStep& leaf, int64_t out_row, int flag) {
-        run.issue({}, [&](const void* p) { return t->launch_tall_nuts(st, p, &na, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag); });
+        run.issue({}, [&](const void* p) {
+            return warm ? t->launch_tall_nuts_tuned(st, p, &nt, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag)
+                        : t->launch_tall_nuts(st, p, &na, phase, iter, leaf.s, leaf.d, leaf.i, out_row, flag);
+        });
     };
     const lr::NutsStep none{};
     run.update(lr::KIND_HMC, lr::PH_LOAD, 0, -1, 0);
@@ -349,6 +362,10 @@ int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpe
     N(lr::NPH_BEGIN, o->iter_offset, none, -1, 1);
     const int64_t total = o->iters * o->thin;
     for (int64_t tt = 0; tt < total && !run.rc; ++tt) {
+        if (warm) {
+            nt.astat = warm->astat(tt);
+            if (tt > 0) N(lr::NPH_CARRY, o->iter_offset + tt, none, -1, 0);
+        }
         for (lr::NutsSched sch(max_depth); !sch.done() && !run.rc;) {
             const lr::NutsStep leaf = sch.cur();
             run.partial(1, 1);
@@ -361,7 +378,9 @@ int do_nuts_stepwise_t(lr_model* m, const Plan& pl, hipStream_t st, const RunSpe
             sch.advance(building);
         }
         const int64_t out_row = ((tt + 1) % o->thin == 0) ? (tt + 1) / o->thin - 1 : -1;
-        N(lr::NPH_END, o->iter_offset + tt, none, out_row, tt + 1 < total);
+        N(lr::NPH_END, o->iter_offset + tt, none, out_row, !warm && tt + 1 < total);
+        if (warm && !run.rc)
+            if (const int rca = warm->after(tt, a.x, P, nt.astat)) return rca;
     }
     N(lr::NPH_STORE, 0, none, -1, 0);
     if (run.rc) return fail(LR_ERR_HIP, "stepwise NUTS launch failed (%d): %s", run.rc, hipGetErrorString(hipGetLastError()));
@@ -393,8 +412,8 @@ int do_eval_stepwise(lr_model* m, const Plan& pl, hipStream_t st, int64_t C, con
 }
 
 int do_nuts_stepwise(lr_model* m, const Plan& pl, hipStream_t st, const RunSpec& rs, const lr_run_opts* o, int max_depth, void* state, void* out, void* counters,
-                     int8_t* depth_out) {
-    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_nuts_stepwise_t, m, pl, st, rs, o, max_depth, state, out, counters, depth_out)
+                     int8_t* depth_out, const NutsWarm* warm = nullptr) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, m->dtype, m->P, do_nuts_stepwise_t, m, pl, st, rs, o, max_depth, state, out, counters, depth_out, warm)
     return bad_width(m);
 }
 

@@ -84,6 +84,8 @@ struct InstTable {
     // NUTS on the stepwise engine (lr_tall_nuts.h): one update launch of k_tall_nuts_update; `tall_args` is a TallArgs<T,P>, `nuts_args` a
     // NutsTallArgs<T>, `phase` a NutsTallPhase, (s, d, i) the leaf of lr_nuts_sched.h; every width of the stepwise engine has it
     int (*launch_tall_nuts)(hipStream_t, const void* tall_args, const void* nuts_args, int phase, int64_t iter, int s, int d, int i, int64_t out_row, int flag);
+    // ... k_tall_nuts_update_tuned (the warm-up): `nuts_args` is a NutsTallTunedArgs<T,P>, and `phase` may be NPH_CARRY
+    int (*launch_tall_nuts_tuned)(hipStream_t, const void* tall_args, const void* nuts_args, int phase, int64_t iter, int s, int d, int i, int64_t out_row, int flag);
 };
 
 }  // namespace lr

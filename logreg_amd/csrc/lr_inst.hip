@@ -310,7 +310,7 @@ int launch_pg(const LaunchCfg* cfg, int64_t C, const void* model_args, const voi
 }
 
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg, &launch_tall_nuts_t<T, P>};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg, &launch_tall_nuts_t<T, P>, &launch_tall_nuts_t<T, P, true>};
 
 }  // namespace
 }  // namespace lr

@@ -106,7 +106,7 @@ int launch_tall_update(hipStream_t st, int kind, int phase, int64_t iter, int64_
     return check(hipGetLastError());
 }
 
-const InstTable kTable = {LR_DTYPE, P, 0, nullptr, nullptr, nullptr, &launch_tall_partial, &launch_tall_update, &launch_tall_traj, nullptr, nullptr, nullptr, nullptr, &launch_tall_nuts_t<T, P>};
+const InstTable kTable = {LR_DTYPE, P, 0, nullptr, nullptr, nullptr, &launch_tall_partial, &launch_tall_update, &launch_tall_traj, nullptr, nullptr, nullptr, nullptr, &launch_tall_nuts_t<T, P>, &launch_tall_nuts_t<T, P, true>};
 
 }  // namespace
 }  // namespace lr

@@ -524,7 +524,8 @@ int make_plan(const PlanReq& q, Plan* out) {
 // else is refused with the reason: wide models, a forced mode or lane count the family does not have, rows and checkpoints beyond the
 // LDS.  The LDS figure is the rows + the U-turn checkpoints at `max_depth`.  Under the diagonal metric the caller may ask for the
 // stepwise engine instead (LR_MODE_STEPWISE: plan_nuts_stepwise below, reached from plan_run; the refusals of LR_MODE_AUTO say so);
-// under a dense metric, and for the warm-up, the stepwise (tall-data) engine has no NUTS kernel.
+// under a dense metric, and for lr_adapt_run's warm-up, the stepwise (tall-data) engine has no NUTS kernel (the warm-up on that engine is
+// lr_tall_adapt_run's, which plans with plan_nuts_stepwise too).
 size_t nuts_lds_bytes(const lr_model* m, int max_depth) {
     return lds_rows_bytes(m) + (size_t)2 * max_depth * ((m->P + 15) / 16) * 256 * m->esize();
 }
@@ -558,8 +559,9 @@ int plan_nuts(const lr_model* m, int group, int mode, int max_depth, Plan* out, 
 // for -- p > 32, or rows and checkpoints (at LR_NUTS_MAX_DEPTH, whatever the call's max_depth: one rule for lr_plan_run and the run) beyond
 // the LDS: the stepwise plan of plan_wide / plan_tall -- group = row slices, rows_per_lane = slice length, one part.  A shape the fused
 // kernel takes keeps its refusal of this mode: nothing that ran, or was refused, before this path existed behaves differently.
+bool nuts_fused_takes(const lr_model* m) { return m->P <= 32 && nuts_lds_bytes(m, LR_NUTS_MAX_DEPTH) <= kLdsBudget; }  // (lr_tall_adapt_create asks too)
 int plan_nuts_stepwise(const lr_model* m, const lr_run_opts* o, Plan* out) {
-    if (m->P <= 32 && nuts_lds_bytes(m, LR_NUTS_MAX_DEPTH) <= kLdsBudget)
+    if (nuts_fused_takes(m))
         return fail(LR_ERR_UNSUPPORTED, "NUTS: the stepwise (tall-data) engine takes NUTS only where the fused kernel cannot (p > 32, or rows beyond the LDS); "
                     "here (n = %lld, p = %d) NUTS runs with the rows in LDS", (long long)m->n, m->p);
     if (!m->table || !m->table->launch_tall_nuts) return fail(LR_ERR_UNSUPPORTED, "NUTS: no stepwise kernel for padded p = %d", m->P);
