@@ -11,71 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "logreg_hip.h"
-#include "logreg_hip_adapt.h"
-
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_on(void* stream);
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_waits();
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_live_streams();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-void hipstub_set_devices(int n);
-long hipstub_wrong_device();
-}
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)                                                  \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                      \
-            std::printf("  (last error: %s)\n", lr_last_error());          \
-            ++g_fail;                                                      \
-        }                                                                  \
-    } while (0)
-
-struct Dev {  // a device buffer through the ABI's own allocator
-    void* p = nullptr;
-    explicit Dev(size_t bytes) { if (lr_malloc(0, bytes, &p) != LR_OK) p = nullptr; }
-    ~Dev() { if (p) lr_free(0, p); }
-};
-
-static lr_model* model(int dtype, int p, int64_t n = 50) {
-    std::vector<double> X((size_t)n * p), y((size_t)n), sd((size_t)p, 1.0);
-    for (int64_t i = 0; i < n; ++i) {
-        y[i] = (double)(i & 1);
-        for (int j = 0; j < p; ++j) X[i * p + j] = j == 0 ? 1.0 : 0.01 * (double)((i * 7 + j * 3) % 13) - 0.06;
-    }
-    lr_model* m = nullptr;
-    EXPECT(lr_model_create(X.data(), y.data(), n, p, sd.data(), dtype, 0, &m) == LR_OK && m, "model (dtype %d, p %d)", dtype, p);
-    return m;
-}
-
-static lr_run_opts run_opts(int64_t C, int on_device, void* stream) {
-    lr_run_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.n_chains = C;
-    o.thin = 1;
-    o.iters = 1;
-    o.seed = 9;
-    o.mode = -1;  // LR_MODE_AUTO
-    o.on_device = on_device;
-    o.stream = stream;
-    return o;
-}
-
-static lr_adapt_opts adapt_opts(int W) {
-    lr_adapt_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.W = W;
-    o.adapt_metric = 1;
-    return o;
-}
+#include "harness.h"
 
 static void schedule() {
     int32_t ends[LR_ADAPT_MAX_WINDOWS], n = -1, init = -1;
@@ -168,9 +104,8 @@ static void failing_allocations(int dtype, int p, int64_t C) {
     EXPECT(hipstub_live_allocs() == live0, "%ld device buffers outlive the handle", hipstub_live_allocs() - live0);
     EXPECT(in_create >= 1 && in_run >= 5 && in_regrow >= 3 && in_regrow <= in_run, "allocations %ld / %ld / %ld", in_create, in_run, in_regrow);
     for (long k = 1; k <= in_create; ++k) {
-        hipstub_fail_malloc_at(k);
-        const int rc = lr_adapt_create(m, C, &ao, &h);
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = lr_adapt_create(m, C, &ao, &h); }
         EXPECT(rc == LR_ERR_NOMEM && !h, "allocation %ld of %ld of create fails: rc %d", k, in_create, rc);
         if (h) lr_adapt_destroy(h);
         h = nullptr;
@@ -182,9 +117,8 @@ static void failing_allocations(int dtype, int p, int64_t C) {
             if (regrow) EXPECT(lr_adapt_run(h, state.data(), 2, 5, &ho, out.data(), cnt.data(), depth.data(), astat.data()) == LR_OK, "run");
             const int64_t before = regrow ? 2 : 0;
             const long l0 = hipstub_launches();
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_adapt_run(h, state.data(), 9, 5, &ho, out.data(), cnt.data(), depth.data(), astat.data());
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_adapt_run(h, state.data(), 9, 5, &ho, out.data(), cnt.data(), depth.data(), astat.data()); }
             EXPECT(rc == LR_ERR_NOMEM && hipstub_launches() == l0, "allocation %ld of run fails (regrow %d): rc %d, %ld launches", k, regrow, rc, hipstub_launches() - l0);
             EXPECT(lr_adapt_result(h, nullptr, nullptr, &info) == LR_OK && info.iterations == before, "the count stays %lld after a failed run (%lld)", (long long)before, (long long)info.iterations);
             EXPECT(lr_adapt_run(h, state.data(), 9, 5, &ho, out.data(), cnt.data(), depth.data(), astat.data()) == LR_OK && lr_adapt_result(h, nullptr, nullptr, &info) == LR_OK &&
@@ -297,7 +231,6 @@ static void errors() {
 }
 
 int main() {
-    const long live0 = hipstub_live_allocs();
     void* stream = nullptr;
     EXPECT(lr_stream_create(0, &stream) == LR_OK, "stream");
     schedule();
@@ -311,9 +244,5 @@ int main() {
         }
     errors();
     EXPECT(lr_stream_destroy(0, stream) == LR_OK, "stream destroy");
-    EXPECT(hipstub_live_allocs() == live0 && hipstub_live_streams() == 0, "%ld device buffers, %ld streams left", hipstub_live_allocs() - live0, hipstub_live_streams());
-    EXPECT(hipstub_bad_launches() == 0 && hipstub_bad_waits() == 0 && hipstub_wrong_device() == 0, "%ld bad launches, %ld bad waits, %ld on the wrong device", hipstub_bad_launches(),
-           hipstub_bad_waits(), hipstub_wrong_device());
-    std::printf("adapt harness: %ld kernel launches (%ld k_adapt_update), %d failures\n", hipstub_launches(), hipstub_launches_of("k_adapt_update"), g_fail);
-    return g_fail ? 1 : 0;
+    return finish("adapt harness", "k_adapt_update");
 }

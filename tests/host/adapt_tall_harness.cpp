@@ -11,58 +11,9 @@
 
 #include "lr_model.h"  // (the model handle: its stepwise workspace is filled by hand for the tally that never reaches zero)
 #include "logreg_hip_adapt_tall.h"
+#include "harness.h"
 
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_waits();
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-long hipstub_wrong_device();
-}
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)                                                  \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                      \
-            std::printf("  (last error: %s)\n", lr_last_error());          \
-            ++g_fail;                                                      \
-        }                                                                  \
-    } while (0)
-
-static lr_model* model(int dtype, int p, int64_t n) {
-    std::vector<double> X((size_t)n * p), y((size_t)n), sd((size_t)p, 1.0);
-    for (int64_t i = 0; i < n; ++i) {
-        y[i] = (double)(i & 1);
-        for (int j = 0; j < p; ++j) X[i * p + j] = j == 0 ? 1.0 : 0.01 * (double)((i * 7 + j * 3) % 13) - 0.06;
-    }
-    lr_model* m = nullptr;
-    EXPECT(lr_model_create(X.data(), y.data(), n, p, sd.data(), dtype, 0, &m) == LR_OK && m, "model (dtype %d, p %d)", dtype, p);
-    return m;
-}
-
-static lr_run_opts run_opts(int64_t C) {
-    lr_run_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.n_chains = C;
-    o.thin = 1;
-    o.iters = 1;
-    o.seed = 9;
-    o.mode = LR_MODE_STEPWISE;
-    return o;
-}
-
-static lr_adapt_opts adapt_opts(int W) {
-    lr_adapt_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.W = W;
-    o.adapt_metric = 1;
-    return o;
-}
+static lr_run_opts stepwise_opts(int64_t C) { return run_opts(C, 0, nullptr, 1, LR_MODE_STEPWISE); }
 
 struct Counts {
     long all, update, load, apart, aupd, partial = 0;
@@ -96,7 +47,7 @@ static void shapes() {
         EXPECT(lr_tall_adapt_create(m, 8, &ao, &h) == LR_OK && h, "create (%s)", which == 0 ? "p = 40" : "rows beyond the LDS");
         if (h) {
             std::vector<double> state((size_t)8 * p, 0.0), stats(4096, 0.0);
-            lr_run_opts o = run_opts(8);
+            lr_run_opts o = stepwise_opts(8);
             const long l0 = hipstub_launches(), m0 = hipstub_mallocs();
             lr_run_opts b = o;
             b.mode = LR_MODE_AUTO;
@@ -119,7 +70,7 @@ static void shapes() {
     EXPECT(lr_adapt_create(narrow, 8, &ao, &h) == LR_OK && h, "a fused handle");
     if (h) {
         std::vector<float> st(8 * 5, 0.f);
-        lr_run_opts o = run_opts(8);
+        lr_run_opts o = stepwise_opts(8);
         EXPECT(lr_tall_adapt_run(h, st.data(), 1, 5, &o, nullptr, nullptr, nullptr, nullptr) == LR_ERR_INVALID && std::strstr(lr_last_error(), "lr_tall_adapt_create") != nullptr, "a fused handle is refused");
         lr_adapt_destroy(h);
     }
@@ -140,7 +91,7 @@ static void launches(int dtype, int p, int64_t n, int64_t C, int md, bool never_
     std::memset(cnt.data(), 0, cnt.size() * sizeof(lr_nuts_counters));
     std::vector<int8_t> depth((size_t)W * C, 0);
     std::vector<double> astat((size_t)W * C, 0.0);
-    lr_run_opts o = run_opts(C);
+    lr_run_opts o = stepwise_opts(C);
     EXPECT(lr_tall_adapt_run(h, state.data(), 1, md, &o, out.data(), cnt.data(), depth.data(), astat.data()) == LR_OK, "a first call (it allocates the workspace)");
     if (never_zero)  // no-op kernels never write the tally: every read of it gives 0xFFFFFFFF chains still building
         for (auto& w : m->ws) std::memset(w.p, 0xFF, w.bytes);
@@ -178,7 +129,7 @@ static void failing_allocations(int dtype, int p, int64_t n, int64_t C) {
     std::memset(cnt.data(), 0, cnt.size() * sizeof(lr_nuts_counters));
     std::vector<int8_t> depth((size_t)W * C, 0);
     std::vector<double> astat((size_t)W * C, 0.0);
-    lr_run_opts o = run_opts(C);
+    lr_run_opts o = stepwise_opts(C);
     const long live0 = hipstub_live_allocs();
     long m0 = hipstub_mallocs();
     EXPECT(lr_tall_adapt_create(m, C, &ao, &h) == LR_OK && h, "create");
@@ -186,9 +137,8 @@ static void failing_allocations(int dtype, int p, int64_t n, int64_t C) {
     lr_adapt_destroy(h);
     h = nullptr;
     for (long k = 1; k <= in_create; ++k) {
-        hipstub_fail_malloc_at(k);
-        const int rc = lr_tall_adapt_create(m, C, &ao, &h);
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = lr_tall_adapt_create(m, C, &ao, &h); }
         EXPECT(rc == LR_ERR_NOMEM && !h && hipstub_live_allocs() == live0, "allocation %ld of create fails: rc %d", k, rc);
     }
     // a run with host pointers allocates five staging buffers and, the first time on a model, the engine's workspace; a longer run grows them
@@ -207,9 +157,8 @@ static void failing_allocations(int dtype, int p, int64_t n, int64_t C) {
             if (regrow) EXPECT(lr_tall_adapt_run(h, state.data(), 2, 4, &o, out.data(), cnt.data(), depth.data(), astat.data()) == LR_OK, "run");
             const int64_t before = regrow ? 2 : 0;
             const long l0 = hipstub_launches();
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_tall_adapt_run(h, state.data(), 9, regrow ? 6 : 4, &o, out.data(), cnt.data(), depth.data(), astat.data());
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_tall_adapt_run(h, state.data(), 9, regrow ? 6 : 4, &o, out.data(), cnt.data(), depth.data(), astat.data()); }
             EXPECT(rc == LR_ERR_NOMEM && hipstub_launches() == l0, "allocation %ld of %ld of a run fails (regrow %d): rc %d, %ld launches", k, in_run, regrow, rc, hipstub_launches() - l0);
             EXPECT(lr_adapt_result(h, nullptr, nullptr, &info) == LR_OK && info.iterations == before, "the count stays %lld after a failed run (%lld)", (long long)before, (long long)info.iterations);
             EXPECT(lr_tall_adapt_run(h, state.data(), 9, regrow ? 6 : 4, &o, out.data(), cnt.data(), depth.data(), astat.data()) == LR_OK && lr_adapt_result(h, nullptr, nullptr, &info) == LR_OK &&
@@ -224,7 +173,6 @@ static void failing_allocations(int dtype, int p, int64_t n, int64_t C) {
 }
 
 int main() {
-    const long live0 = hipstub_live_allocs();
     shapes();
     for (int md : {1, 2, 4, 6}) {
         launches(LR_F32, 40, 64, 37, md, false);
@@ -234,9 +182,5 @@ int main() {
     }
     failing_allocations(LR_F32, 40, 64, 300);
     failing_allocations(LR_F64, 20, 1200, 9);
-    EXPECT(hipstub_live_allocs() == live0, "%ld device buffers left", hipstub_live_allocs() - live0);
-    EXPECT(hipstub_bad_launches() == 0 && hipstub_bad_waits() == 0 && hipstub_wrong_device() == 0, "%ld bad launches, %ld bad waits, %ld on the wrong device", hipstub_bad_launches(),
-           hipstub_bad_waits(), hipstub_wrong_device());
-    std::printf("adapt tall harness: %ld kernel launches (%ld k_tall_nuts_update), %d failures\n", hipstub_launches(), hipstub_launches_of("k_tall_nuts_update"), g_fail);
-    return g_fail ? 1 : 0;
+    return finish("adapt tall harness", "k_tall_nuts_update");
 }

@@ -12,39 +12,8 @@
 #include <cstring>
 #include <vector>
 
-#include "logreg_hip.h"
+#include "harness.h"
 #include "logreg_hip_cov.h"
-
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_on(void* stream);
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_waits();
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_live_streams();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-void hipstub_set_devices(int n);
-long hipstub_wrong_device();
-}
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)                                                  \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                      \
-            std::printf("  (last error: %s)\n", lr_last_error());          \
-            ++g_fail;                                                      \
-        }                                                                  \
-    } while (0)
-
-struct Dev {  // a device buffer through the ABI's own allocator
-    void* p = nullptr;
-    explicit Dev(size_t bytes) { if (lr_malloc(0, bytes, &p) != LR_OK) p = nullptr; }
-    ~Dev() { if (p) lr_free(0, p); }
-};
 
 struct Shape {
     int dtype;
@@ -141,9 +110,8 @@ static void failing_allocations(const Shape& s, const void* zeros) {
     EXPECT(hipstub_live_allocs() == live0, "%ld device buffers outlive the accumulator", hipstub_live_allocs() - live0);
     EXPECT(in_create >= 1 && in_feed >= 1 && in_regrow >= 1 && in_regrow <= in_feed && in_result >= 1, "allocations %ld / %ld / %ld / %ld", in_create, in_feed, in_regrow, in_result);
     for (long k = 1; k <= in_create; ++k) {
-        hipstub_fail_malloc_at(k);
-        const int rc = create(s, &h);
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = create(s, &h); }
         EXPECT(rc == LR_ERR_NOMEM && !h, "allocation %ld of %ld of create fails: rc %d", k, in_create, rc);
         if (h) lr_cov_destroy(h);
         h = nullptr;
@@ -154,9 +122,8 @@ static void failing_allocations(const Shape& s, const void* zeros) {
             EXPECT(create(s, &h) == LR_OK && h, "fresh");
             if (regrow) EXPECT(lr_cov_accumulate(h, zeros, 3, 0, nullptr) == LR_OK, "feed");
             const int64_t before = regrow ? 3 : 0;
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_cov_accumulate(h, zeros, 40, 0, nullptr);
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_cov_accumulate(h, zeros, 40, 0, nullptr); }
             EXPECT(rc == LR_ERR_NOMEM, "allocation %ld of accumulate fails (regrow %d): rc %d", k, regrow, rc);
             EXPECT(result(s, h, &n, f) == LR_OK && n == before, "the count stays %lld after a failed accumulate (n %lld)", (long long)before, (long long)n);
             EXPECT(lr_cov_accumulate(h, zeros, 40, 0, nullptr) == LR_OK && result(s, h, &n, f) == LR_OK && n == before + 40, "usable after a failed accumulate");
@@ -166,10 +133,9 @@ static void failing_allocations(const Shape& s, const void* zeros) {
         }
     for (long k = 1; k <= in_result; ++k) {
         EXPECT(create(s, &h) == LR_OK && h && lr_cov_accumulate(h, zeros, 43, 0, nullptr) == LR_OK, "fresh");
-        hipstub_fail_malloc_at(k);
         n = -1;
-        const int rc = result(s, h, &n, f);  // (the k-th allocation of the whole sequence of result calls)
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = result(s, h, &n, f); }  // (the k-th allocation of the whole sequence of result calls)
         EXPECT(rc == LR_ERR_NOMEM && n == 43, "allocation %ld of %ld of result fails: rc %d, n %lld", k, in_result, rc, (long long)n);
         EXPECT(result(s, h, &n, f) == LR_OK && n == 43 && lr_cov_accumulate(h, zeros, 2, 0, nullptr) == LR_OK, "usable after a failed result");
         lr_cov_destroy(h);
@@ -225,7 +191,6 @@ int main() {
     const int64_t bigC = 8192;
     const int bigp = 64;
     const std::vector<unsigned char> zeros((size_t)65 * bigC * bigp * 8, 0);
-    const long live0 = hipstub_live_allocs();
     void* stream = nullptr;
     EXPECT(lr_stream_create(0, &stream) == LR_OK, "stream");
     for (int dtype : {LR_F32, LR_F64})
@@ -236,9 +201,5 @@ int main() {
     two_pieces(Shape{LR_F64, bigC, bigp}, 64, zeros.data(), stream);
     errors();
     EXPECT(lr_stream_destroy(0, stream) == LR_OK, "stream destroy");
-    EXPECT(hipstub_live_allocs() == live0 && hipstub_live_streams() == 0, "%ld device buffers, %ld streams left", hipstub_live_allocs() - live0, hipstub_live_streams());
-    EXPECT(hipstub_bad_launches() == 0 && hipstub_bad_waits() == 0 && hipstub_wrong_device() == 0, "%ld bad launches, %ld bad waits, %ld on the wrong device", hipstub_bad_launches(),
-           hipstub_bad_waits(), hipstub_wrong_device());
-    std::printf("cov harness: %ld kernel launches (%ld k_cov_accumulate), %d failures\n", hipstub_launches(), hipstub_launches_of("k_cov_accumulate"), g_fail);
-    return g_fail ? 1 : 0;
+    return finish("cov harness", "k_cov_accumulate");
 }

@@ -12,63 +12,8 @@
 #include <cstring>
 #include <vector>
 
-#include "logreg_hip.h"
+#include "harness.h"
 #include "logreg_hip_dense.h"
-
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_on(void* stream);
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_waits();
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_live_streams();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-void hipstub_set_devices(int n);
-long hipstub_wrong_device();
-}
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)                                                  \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                      \
-            std::printf("  (last error: %s)\n", lr_last_error());          \
-            ++g_fail;                                                      \
-        }                                                                  \
-    } while (0)
-
-struct Dev {
-    void* p = nullptr;
-    explicit Dev(size_t bytes) { if (lr_malloc(0, bytes, &p) != LR_OK) p = nullptr; }
-    ~Dev() { if (p) lr_free(0, p); }
-};
-
-static lr_model* model(int dtype, int p, int64_t n = 50) {
-    std::vector<double> X((size_t)n * p), y((size_t)n), sd((size_t)p, 1.0);
-    for (int64_t i = 0; i < n; ++i) {
-        y[i] = (double)(i & 1);
-        for (int j = 0; j < p; ++j) X[i * p + j] = j == 0 ? 1.0 : 0.01 * (double)((i * 7 + j * 3) % 13) - 0.06;
-    }
-    lr_model* m = nullptr;
-    EXPECT(lr_model_create(X.data(), y.data(), n, p, sd.data(), dtype, 0, &m) == LR_OK && m, "model (dtype %d, p %d)", dtype, p);
-    return m;
-}
-
-static lr_run_opts run_opts(int64_t C, int on_device, void* stream, int64_t iters = 2) {
-    lr_run_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.n_chains = C;
-    o.thin = 1;
-    o.iters = iters;
-    o.seed = 9;
-    o.mode = -1;  // LR_MODE_AUTO
-    o.on_device = on_device;
-    o.stream = stream;
-    return o;
-}
 
 // a well-conditioned symmetric positive definite matrix: a tridiagonal correlation scaled by unequal standard deviations
 static std::vector<double> spd(int p, double off = 0.4) {
@@ -134,7 +79,7 @@ static void runs(int dtype, int p, int64_t C, void* stream) {
     std::memset(cnt.data(), 0, cnt.size() * sizeof(lr_nuts_counters));
     std::vector<int8_t> depth((size_t)2 * C, 0);
     std::vector<double> stats((size_t)4 * C * 2 * p, 0.0);
-    lr_run_opts o = run_opts(C, 0, nullptr);
+    lr_run_opts o = run_opts(C, 0, nullptr, 2);
     const long k0 = hipstub_launches_of("k_nuts_dense"), d0 = hipstub_launches_of("k_nuts<");
     long m0 = hipstub_mallocs();
     EXPECT(lr_run_nuts_dense(m, state.data(), 0.01, D, sig.data(), &o, out.data(), cnt.data(), depth.data()) == LR_OK, "host, every array");
@@ -155,7 +100,7 @@ static void runs(int dtype, int p, int64_t C, void* stream) {
     EXPECT(lr_run_nuts_dense(m, state.data(), 0.01, D, sig.data(), &oz, out.data(), cnt.data(), depth.data()) == LR_OK, "no iterations");
     Dev dstate(C * p * es), dout((size_t)2 * C * p * es), dcnt(C * sizeof(lr_nuts_counters)), ddepth((size_t)2 * C);
     EXPECT(dstate.p && dout.p && dcnt.p && ddepth.p, "device arrays");
-    lr_run_opts od = run_opts(C, 1, stream);
+    lr_run_opts od = run_opts(C, 1, stream, 2);
     const long s0 = hipstub_launches_on(stream);
     m0 = hipstub_mallocs();
     EXPECT(lr_run_nuts_dense(m, dstate.p, 0.01, D, sig.data(), &od, dout.p, (lr_nuts_counters*)dcnt.p, (int8_t*)ddepth.p) == LR_OK, "device, every array");
@@ -170,9 +115,8 @@ static void runs(int dtype, int p, int64_t C, void* stream) {
         const long live0 = hipstub_live_allocs();
         for (long k = 1; k <= first; ++k) {
             const long l0 = hipstub_launches();
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_run_nuts_dense(fresh, state.data(), 0.01, D, sig.data(), &os, out.data(), cnt.data(), depth.data());
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_run_nuts_dense(fresh, state.data(), 0.01, D, sig.data(), &os, out.data(), cnt.data(), depth.data()); }
             EXPECT(rc == LR_ERR_NOMEM && hipstub_launches() == l0, "allocation %ld of %ld fails: rc %d", k, first, rc);
             EXPECT(hipstub_live_allocs() <= live0 + 1, "allocation %ld fails: %ld buffers beyond the model's factor image", k, hipstub_live_allocs() - live0);
         }
@@ -191,7 +135,7 @@ static void run_errors() {
     std::vector<float> st(8 * 5, 0.f), out(2 * 8 * 5, 0.f);
     std::vector<lr_nuts_counters> cnt(8);
     std::vector<int8_t> dep(16);
-    lr_run_opts o = run_opts(8, 0, nullptr);
+    lr_run_opts o = run_opts(8, 0, nullptr, 2);
     const long mallocs0 = hipstub_mallocs(), l0 = hipstub_launches();
     auto refused = [&](int rc, const char* word) { return rc == LR_ERR_INVALID && std::strstr(lr_last_error(), word) != nullptr; };
     EXPECT(refused(lr_run_nuts_dense(nullptr, st.data(), 0.1, 3, sig.data(), &o, nullptr, nullptr, nullptr), "NULL"), "NULL model");
@@ -240,22 +184,13 @@ static void run_errors() {
     lr_model_destroy(wide);
 }
 
-static lr_adapt_opts adapt_opts(int W, int adapt_metric) {
-    lr_adapt_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.W = W;
-    o.adapt_metric = adapt_metric;
-    o.eps0 = 0.25;
-    return o;
-}
-
 static void warmup(int dtype, int p, int64_t C, int W, int adapt_metric, void* stream) {
     lr_model* m = model(dtype, p);
     if (!m) return;
     const size_t es = dtype == LR_F32 ? 4 : 8;
     const std::vector<double> sig = spd(p);
     lr_adapt* h = nullptr;
-    lr_adapt_opts ao = adapt_opts(W, adapt_metric);
+    lr_adapt_opts ao = adapt_opts(W, adapt_metric, 0.25);
     const long live0 = hipstub_live_allocs();
     long m0 = hipstub_mallocs();
     EXPECT(lr_dense_adapt_create(m, C, &ao, sig.data(), &h) == LR_OK && h, "create (C %lld, p %d, W %d)", (long long)C, p, W);
@@ -276,7 +211,7 @@ static void warmup(int dtype, int p, int64_t C, int W, int adapt_metric, void* s
         std::memset(cnt.data(), 0, cnt.size() * sizeof(lr_nuts_counters));
         std::vector<int8_t> depth((size_t)W * C, 0);
         std::vector<double> astat((size_t)W * C, 0.0);
-        lr_run_opts ho = run_opts(C, 0, nullptr), dopt = run_opts(C, 1, stream);
+        lr_run_opts ho = run_opts(C, 0, nullptr, 2), dopt = run_opts(C, 1, stream, 2);
         const long n0 = hipstub_launches(), k0 = hipstub_launches_of("k_nuts_dense"), c0 = hipstub_launches_of("k_dense_comoment"), d0 = hipstub_launches_of("k_nuts<");
         const int64_t first = W > 8 ? 7 : W - 1;
         EXPECT(lr_dense_adapt_run(h, state.data(), 0, 5, &ho, nullptr, nullptr, nullptr, nullptr) == LR_OK, "nothing to do");
@@ -304,9 +239,8 @@ static void warmup(int dtype, int p, int64_t C, int W, int adapt_metric, void* s
     }
     EXPECT(hipstub_live_allocs() == live0, "%ld device buffers outlive the handle", hipstub_live_allocs() - live0);
     for (long k = 1; k <= in_create; ++k) {
-        hipstub_fail_malloc_at(k);
-        const int rc = lr_dense_adapt_create(m, C, &ao, sig.data(), &h);
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = lr_dense_adapt_create(m, C, &ao, sig.data(), &h); }
         EXPECT(rc == LR_ERR_NOMEM && !h, "allocation %ld of %ld of create fails: rc %d", k, in_create, rc);
         if (h) lr_dense_adapt_destroy(h);
         h = nullptr;
@@ -320,7 +254,7 @@ static void warmup_errors() {
     if (!m) return;
     const std::vector<double> sig = spd(5);
     lr_adapt* h = nullptr;
-    lr_adapt_opts ao = adapt_opts(40, 1);
+    lr_adapt_opts ao = adapt_opts(40, 1, 0.25);
     auto refused = [&](int rc, const char* word) { return rc == LR_ERR_INVALID && std::strstr(lr_last_error(), word) != nullptr; };
     const long mallocs0 = hipstub_mallocs();
     EXPECT(refused(lr_dense_adapt_create(nullptr, 8, &ao, sig.data(), &h), "NULL") && refused(lr_dense_adapt_create(m, 8, nullptr, sig.data(), &h), "NULL") &&
@@ -349,7 +283,7 @@ static void warmup_errors() {
     EXPECT(lr_adapt_create(m, 8, &ao, &h) == LR_OK && h, "a diagonal handle");
     if (h) {
         std::vector<float> st(8 * 5, 0.f);
-        lr_run_opts o = run_opts(8, 0, nullptr);
+        lr_run_opts o = run_opts(8, 0, nullptr, 2);
         EXPECT(refused(lr_dense_adapt_run(h, st.data(), 1, 5, &o, nullptr, nullptr, nullptr, nullptr), "not one of") && refused(lr_dense_adapt_result(h, nullptr, nullptr, nullptr), "not one of") &&
                    refused(lr_dense_adapt_trace(h, nullptr, nullptr), "not one of"), "a diagonal handle is refused by the dense calls");
         lr_adapt_destroy(h);
@@ -361,7 +295,6 @@ static void warmup_errors() {
 }
 
 int main() {
-    const long live0 = hipstub_live_allocs();
     void* stream = nullptr;
     EXPECT(lr_stream_create(0, &stream) == LR_OK, "stream");
     factor();
@@ -377,9 +310,5 @@ int main() {
     run_errors();
     warmup_errors();
     EXPECT(lr_stream_destroy(0, stream) == LR_OK, "stream destroy");
-    EXPECT(hipstub_live_allocs() == live0 && hipstub_live_streams() == 0, "%ld device buffers, %ld streams left", hipstub_live_allocs() - live0, hipstub_live_streams());
-    EXPECT(hipstub_bad_launches() == 0 && hipstub_bad_waits() == 0 && hipstub_wrong_device() == 0, "%ld bad launches, %ld bad waits, %ld on the wrong device", hipstub_bad_launches(),
-           hipstub_bad_waits(), hipstub_wrong_device());
-    std::printf("dense harness: %ld kernel launches (%ld k_nuts_dense), %d failures\n", hipstub_launches(), hipstub_launches_of("k_nuts_dense"), g_fail);
-    return g_fail ? 1 : 0;
+    return finish("dense harness", "k_nuts_dense");
 }

@@ -12,7 +12,7 @@
 //   engine_harness threads    two host threads, one model / stream / chain set each, running concurrently (ThreadSanitizer)
 //   engine_harness trace      the launches of the stepwise engine, case by case, as text (tests/test_stepwise_trace_cpu.py compares it with
 //                             tests/golden/stepwise_launch_trace.txt, recorded from the engine before its launch loop was rewritten)
-#include "logreg_hip.h"
+#include "harness.h"
 #include "logreg_hip_acf.h"
 #include "logreg_hip_loo.h"
 #include "logreg_hip_marginals.h"
@@ -30,36 +30,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_on(void* stream);
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_waits();
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_live_streams();
-long hipstub_live_events();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-void hipstub_set_devices(int n);
-long hipstub_work_on_device(int d);
-long hipstub_wrong_device();
-void hipstub_trace_begin();
-long hipstub_trace_end();
-const char* hipstub_trace_record(long i);
-}
-
-static int g_fail = 0;
 static long g_deliberate_bad_waits = 0;  // (scenario_errors asks for the elapsed time of an event it never recorded)
-#define EXPECT(cond, ...)                                                              \
-    do {                                                                               \
-        if (!(cond)) {                                                                 \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond);             \
-            std::printf(__VA_ARGS__);                                                  \
-            std::printf("  (last error: %s)\n", lr_last_error());                      \
-            ++g_fail;                                                                  \
-        }                                                                              \
-    } while (0)
 
 struct Data {
     std::vector<double> X, y, sd;
@@ -79,12 +50,6 @@ static Data make_data(int64_t n, int p, unsigned seed) {
     }
     return d;
 }
-struct Dev {  // a device buffer through the ABI's own allocator
-    void* p = nullptr;
-    explicit Dev(size_t bytes) { if (lr_malloc(0, bytes, &p) != LR_OK) p = nullptr; }
-    ~Dev() { if (p) lr_free(0, p); }
-};
-
 // NUTS on one model: host and device buffers, with and without samples, counters, depths and statistics.  A shape or a forced
 // (mode, group) the family has no kernel for is refused by every call, as lr_plan_run refuses it.
 static void run_nuts(lr_model* m, const Data& d, int64_t C, int dtype, void* stream, int mode, int group) {
@@ -372,9 +337,8 @@ static void scenario_failing_allocations() {
         const long live0 = hipstub_live_allocs();
         for (long k = 1; k <= made; ++k) {
             m = nullptr;
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), s.dtype, 0, &m);
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), s.dtype, 0, &m); }
             EXPECT(rc == LR_ERR_NOMEM && m == nullptr, "allocation %ld of %ld fails (n=%lld p=%d): rc %d", k, made, (long long)s.n, s.p, rc);
             EXPECT(hipstub_live_allocs() == live0, "allocation %ld of %ld fails: %ld device buffers leaked", k, made, hipstub_live_allocs() - live0);
             if (m) lr_model_destroy(m);
@@ -395,9 +359,8 @@ static void scenario_failing_allocations() {
         for (long k = 1; k <= in_run; ++k) {
             EXPECT(lr_model_create(d.X.data(), d.y.data(), d.n, d.p, d.sd.data(), s.dtype, 0, &m) == LR_OK, "fresh model");
             const long before = hipstub_live_allocs();
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_run_hmc(m, st.data(), 0.01, 2, vec.data(), &o, out.data(), acc.data());
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_run_hmc(m, st.data(), 0.01, 2, vec.data(), &o, out.data(), acc.data()); }
             EXPECT(rc == LR_ERR_NOMEM || rc == LR_ERR_HIP, "allocation %ld of %ld inside the run fails: rc %d", k, in_run, rc);
             EXPECT(lr_run_hmc(m, st.data(), 0.01, 2, vec.data(), &o, out.data(), acc.data()) == LR_OK, "the model runs after a failed run");
             lr_model_destroy(m);
@@ -439,9 +402,8 @@ static void scenario_failing_staged_allocations() {
             const long made = hipstub_mallocs() - m0;
             EXPECT(made == c.arrays && hipstub_live_allocs() == live0, "%s: %ld device buffers staged for %ld arrays, %ld left behind", c.what, made, c.arrays, hipstub_live_allocs() - live0);
             for (long k = 1; k <= made; ++k) {
-                hipstub_fail_malloc_at(k);
-                const int rc = c.run();
-                hipstub_fail_malloc_at(-1);
+                int rc;
+                { FailMallocAt failing(k); rc = c.run(); }
                 EXPECT(rc == LR_ERR_NOMEM, "%s: allocation %ld of %ld fails: rc %d", c.what, k, made, rc);
                 EXPECT(hipstub_live_allocs() == live0, "%s: allocation %ld of %ld fails: %ld device buffers leaked", c.what, k, made, hipstub_live_allocs() - live0);
                 EXPECT(c.run() == LR_OK, "%s: the call works after a failed one", c.what);
@@ -674,9 +636,8 @@ static void accumulator_failing_allocations(const Acc& a, const void* zeros) {
     EXPECT(hipstub_live_allocs() == live0, "%s: %ld device buffers outlive the accumulator", a.name.c_str(), hipstub_live_allocs() - live0);
     EXPECT(in_create >= 1 && in_feed >= 1 && in_regrow >= 1 && in_regrow <= in_feed, "%s: allocations %ld / %ld / %ld / %ld", a.name.c_str(), in_create, in_feed, in_regrow, in_result);
     for (long k = 1; k <= in_create; ++k) {
-        hipstub_fail_malloc_at(k);
-        const int rc = a.create();
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = a.create(); }
         EXPECT(rc == LR_ERR_NOMEM && !a.made(), "%s: allocation %ld of %ld of create fails: rc %d", a.name.c_str(), k, in_create, rc);
         if (a.made()) a.destroy();
         EXPECT(hipstub_live_allocs() == live0, "%s: allocation %ld of create fails: %ld device buffers leaked", a.name.c_str(), k, hipstub_live_allocs() - live0);
@@ -686,9 +647,8 @@ static void accumulator_failing_allocations(const Acc& a, const void* zeros) {
             EXPECT(a.create() == LR_OK && a.made(), "%s: fresh", a.name.c_str());
             if (regrow) EXPECT(a.feed(zeros, 3, 0, nullptr) == LR_OK, "%s: feed", a.name.c_str());
             const int64_t before = regrow ? 3 : 0;
-            hipstub_fail_malloc_at(k);
-            const int rc = a.feed(zeros, 40, 0, nullptr);
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = a.feed(zeros, 40, 0, nullptr); }
             EXPECT(rc == LR_ERR_NOMEM, "%s: allocation %ld of accumulate fails (regrow %d): rc %d", a.name.c_str(), k, regrow, rc);
             EXPECT(a.result(&n, &first) == LR_OK && n == before, "%s: the count stays %lld after a failed accumulate (n %lld)", a.name.c_str(), (long long)before, (long long)n);
             EXPECT(a.feed(zeros, 40, 0, nullptr) == LR_OK && a.result(&n, &first) == LR_OK && n == before + 40, "%s: usable after a failed accumulate", a.name.c_str());
@@ -697,9 +657,8 @@ static void accumulator_failing_allocations(const Acc& a, const void* zeros) {
         }
     for (long k = 1; k <= in_result; ++k) {
         EXPECT(a.create() == LR_OK && a.made() && a.feed(zeros, 43, 0, nullptr) == LR_OK, "%s: fresh", a.name.c_str());
-        hipstub_fail_malloc_at(k);
-        const int rc = a.result(&n, &first);
-        hipstub_fail_malloc_at(-1);
+        int rc;
+        { FailMallocAt failing(k); rc = a.result(&n, &first); }
         EXPECT(rc == LR_ERR_NOMEM && n == 43, "%s: allocation %ld of %ld of result fails: rc %d, n %lld", a.name.c_str(), k, in_result, rc, (long long)n);
         EXPECT(a.result(&n, &first) == LR_OK && n == 43 && a.feed(zeros, 2, 0, nullptr) == LR_OK, "%s: usable after a failed result", a.name.c_str());
         a.destroy();
@@ -741,9 +700,8 @@ static void scenario_accumulators() {
         EXPECT(lr_psis(0, zeros.data(), 5000, 3, dtype, 0, table.data(), nullptr) == LR_OK, "psis, the kernel of long tails");
         for (long k = 1; k <= 3; ++k) {
             const long live0 = hipstub_live_allocs();
-            hipstub_fail_malloc_at(k);
-            const int rc = lr_psis(0, zeros.data(), 30, 6, dtype, 0, table.data(), stream);
-            hipstub_fail_malloc_at(-1);
+            int rc;
+            { FailMallocAt failing(k); rc = lr_psis(0, zeros.data(), 30, 6, dtype, 0, table.data(), stream); }
             EXPECT(rc == LR_ERR_NOMEM && hipstub_live_allocs() == live0, "psis: allocation %ld fails: rc %d, %ld leaked", k, rc, hipstub_live_allocs() - live0);
         }
     }

@@ -10,6 +10,8 @@
 // Nothing in the product links this file.
 #include <hip/hip_runtime_api.h>
 
+#include "hip_stub.h"
+
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +64,7 @@ bool live_event(hipEvent_t e) {
 
 }  // namespace
 
-// ---- the books (read by tests/host/engine_harness.cpp)
+// ---- the books (declared in hip_stub.h, read by the harnesses)
 extern "C" {
 long hipstub_launches() { return g_launches.load(); }
 long hipstub_launches_on(void* stream) { return stream ? reinterpret_cast<Stream*>(stream)->launches.load() : g_null_launches.load(); }

@@ -460,8 +460,9 @@ LR_API int lr_comm_create(const void *id, int32_t rank, int32_t world, int devic
         const int fd = shm_open(c->name, O_CREAT | O_RDWR, 0600);
         if (fd < 0 || ftruncate(fd, (off_t)sizeof(twin_seg)) != 0) {
             if (fd >= 0) close(fd);
+            const int rc = fail(LR_ERR_HIP, "shared-memory segment %s of the test double's exchange could not be made", c->name);
             free(c);
-            return fail(LR_ERR_HIP, "shared-memory segment %s of the test double's exchange could not be made", c->name);
+            return rc;
         }
         c->seg = (twin_seg *)mmap(NULL, sizeof(twin_seg), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
         close(fd);

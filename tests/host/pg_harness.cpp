@@ -12,75 +12,26 @@
 #include <string>
 #include <vector>
 
-#include "logreg_hip.h"
+#include "harness.h"
 #include "logreg_hip_pg.h"
 #include "lr_model.h"  // struct lr_model: pg_b
 
-extern "C" {
-long hipstub_launches();
-long hipstub_launches_of(const char* name_part);
-long hipstub_bad_launches();
-long hipstub_live_allocs();
-long hipstub_mallocs();
-void hipstub_fail_malloc_at(long nth);
-}
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)                                                  \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s  -- ", __FILE__, __LINE__, #cond); \
-            std::printf(__VA_ARGS__);                                      \
-            std::printf("  (last error: %s)\n", lr_last_error());          \
-            ++g_fail;                                                      \
-        }                                                                  \
-    } while (0)
-
-struct Dev {
-    void* p = nullptr;
-    explicit Dev(size_t bytes) { if (lr_malloc(0, bytes, &p) != LR_OK) p = nullptr; }
-    ~Dev() { if (p) lr_free(0, p); }
-};
-
-static std::vector<double> g_X, g_y;
-static lr_model* model(int dtype, int p, int64_t n = 50) {
-    g_X.assign((size_t)n * p, 0.0);
-    g_y.assign((size_t)n, 0.0);
-    std::vector<double> sd((size_t)p, 1.5);
-    for (int64_t i = 0; i < n; ++i) {
-        g_y[i] = (double)(i % 3 == 0);
-        for (int j = 0; j < p; ++j) g_X[i * p + j] = j == 0 ? 1.0 : 0.01 * (double)((i * 7 + j * 3) % 13) - 0.06;
-    }
-    lr_model* m = nullptr;
-    EXPECT(lr_model_create(g_X.data(), g_y.data(), n, p, sd.data(), dtype, 0, &m) == LR_OK && m, "model (dtype %d, p %d, n %lld)", dtype, p, (long long)n);
-    return m;
-}
-
-static lr_run_opts run_opts(int64_t C, int on_device, int64_t iters = 2) {
-    lr_run_opts o;
-    std::memset(&o, 0, sizeof(o));
-    o.n_chains = C;
-    o.thin = 1;
-    o.iters = iters;
-    o.seed = 9;
-    o.mode = -1;  // LR_MODE_AUTO
-    o.on_device = on_device;
-    return o;
-}
+static Design g_d;  // the design of the latest model: the_vector_b reads it
+static lr_model* pg_model(int dtype, int p, int64_t n = 50) { return model(dtype, p, n, 1.5, true, &g_d); }
 
 static bool refused(int rc, int code, const char* word) { return rc == code && std::strstr(lr_last_error(), word) != nullptr; }
 
 static void the_vector_b() {
     for (int dtype : {LR_F32, LR_F64})
         for (int p : {1, 3, 8, 20, 32}) {
-            lr_model* m = model(dtype, p, 37);
+            lr_model* m = pg_model(dtype, p, 37);
             if (!m) continue;
             EXPECT((int)m->pg_b.size() == p, "b has p entries");
             for (int j = 0; j < p && j < (int)m->pg_b.size(); ++j) {
                 double want = 0;  // X^T (y - 1/2) of the rows as stored
                 for (int64_t i = 0; i < 37; ++i) {
-                    const double x = dtype == LR_F32 ? (double)(float)g_X[i * p + j] : g_X[i * p + j];
-                    want += (g_y[i] - 0.5) * x;
+                    const double x = dtype == LR_F32 ? (double)(float)g_d.X[i * p + j] : g_d.X[i * p + j];
+                    want += (g_d.y[i] - 0.5) * x;
                 }
                 EXPECT(std::fabs(m->pg_b[j] - want) <= 1e-13 * (1.0 + std::fabs(want)), "b[%d] = %.17g, X^T (y - 1/2) = %.17g (dtype %d, p %d)", j, m->pg_b[j], want, dtype, p);
             }
@@ -89,8 +40,8 @@ static void the_vector_b() {
 }
 
 static void planner() {
-    lr_model* m = model(LR_F32, 8, 200);
-    lr_run_opts o = run_opts(4096, 1);
+    lr_model* m = pg_model(LR_F32, 8, 200);
+    lr_run_opts o = run_opts(4096, 1, nullptr, 2);
     lr_plan_info pi;
     EXPECT(lr_plan_run_info(m, LR_KIND_PG, &o, &pi) == LR_OK && pi.mode == LR_MODE_LDS && pi.group == 16 && pi.split == 0, "Pima's shape plans as lds, 16 lanes");
     int32_t mode = -7, group = -7, rows = -7;
@@ -106,21 +57,21 @@ static void planner() {
     o.mode = LR_MODE_REG;
     EXPECT(refused(lr_plan_run_info(m, LR_KIND_PG, &o, &pi), LR_ERR_UNSUPPORTED, "rows in LDS only"), "mode reg");
     lr_model_destroy(m);
-    o = run_opts(64, 1);
-    m = model(LR_F32, 40, 30);
+    o = run_opts(64, 1, nullptr, 2);
+    m = pg_model(LR_F32, 40, 30);
     EXPECT(refused(lr_plan_run_info(m, LR_KIND_PG, &o, &pi), LR_ERR_UNSUPPORTED, "p = 40 > 32"), "p = 40");
     lr_model_destroy(m);
-    m = model(LR_F32, 8, 20000);
+    m = pg_model(LR_F32, 8, 20000);
     EXPECT(refused(lr_plan_run_info(m, LR_KIND_PG, &o, &pi), LR_ERR_UNSUPPORTED, "bytes of LDS"), "n = 20 000 at p = 8: rows beyond the LDS");
     lr_model_destroy(m);
-    m = model(LR_F32, 2, 65536);
+    m = pg_model(LR_F32, 2, 65536);
     EXPECT(refused(lr_plan_run_info(m, LR_KIND_PG, &o, &pi), LR_ERR_UNSUPPORTED, "n = 65536 >= 65536"), "n = 65 536");
     lr_model_destroy(m);
     // the LDS arithmetic: float64 p = 8 pads a row to 10 doubles; rows + 16 n doubles of staging
-    m = model(LR_F64, 8, 787);  // 787 * (80 + 128) = 163 696 <= 163 840
+    m = pg_model(LR_F64, 8, 787);  // 787 * (80 + 128) = 163 696 <= 163 840
     EXPECT(lr_plan_run_info(m, LR_KIND_PG, &o, &pi) == LR_OK, "787 float64 rows of 8 fit");
     lr_model_destroy(m);
-    m = model(LR_F64, 8, 788);  // 163 904
+    m = pg_model(LR_F64, 8, 788);  // 163 904
     EXPECT(refused(lr_plan_run_info(m, LR_KIND_PG, &o, &pi), LR_ERR_UNSUPPORTED, "163904 bytes of LDS"), "788 do not");
     lr_model_destroy(m);
 }
@@ -128,7 +79,7 @@ static void planner() {
 static void runs() {
     for (int dtype : {LR_F32, LR_F64})
         for (int p : {3, 8, 20, 32}) {
-            lr_model* m = model(dtype, p);
+            lr_model* m = pg_model(dtype, p);
             if (!m) continue;
             const int64_t C = 37, n = 50, iters = 3;
             const size_t es = dtype == LR_F32 ? 4 : 8;
@@ -136,7 +87,7 @@ static void runs() {
             std::vector<lr_pg_counters> cn((size_t)C);
             std::memset(cn.data(), 0, cn.size() * sizeof(lr_pg_counters));
             std::vector<double> stats((size_t)2 * C * 2 * p, 0.0);
-            lr_run_opts o = run_opts(C, 0, iters);
+            lr_run_opts o = run_opts(C, 0, nullptr, iters);
             // refusals, ahead of any device access
             const long m0 = hipstub_mallocs(), l0 = hipstub_launches();
             EXPECT(refused(lr_run_pg(nullptr, state.data(), &o, nullptr, nullptr), LR_ERR_INVALID, "model is NULL"), "no model");
@@ -178,16 +129,15 @@ static void runs() {
             EXPECT(hipstub_live_allocs() == a0, "staging freed");
             // a failing allocation at every allocation of a host-pointer call
             for (long nth = 1; nth <= 3; ++nth) {  // state, out, counters
-                hipstub_fail_malloc_at(nth);
-                const int rc = lr_run_pg(m, state.data(), &o, out.data(), cn.data());
+                int rc;
+                { FailMallocAt failing(nth); rc = lr_run_pg(m, state.data(), &o, out.data(), cn.data()); }
                 EXPECT(refused(rc, LR_ERR_NOMEM, "device allocation failed"), "allocation %ld fails: rc %d", nth, rc);
                 EXPECT(hipstub_live_allocs() == a0, "nothing leaks after allocation %ld failed", nth);
             }
-            hipstub_fail_malloc_at(-1);
             // device pointers
             {
                 Dev ds(state.size()), dout(out.size()), dcn(cn.size() * sizeof(lr_pg_counters)), dom(omega.size());
-                lr_run_opts od = run_opts(C, 1, iters);
+                lr_run_opts od = run_opts(C, 1, nullptr, iters);
                 od.chain_offset = 1000;
                 od.iter_offset = 77;
                 const long k1 = hipstub_launches_of("k_pg");
@@ -204,8 +154,5 @@ int main() {
     the_vector_b();
     planner();
     runs();
-    EXPECT(hipstub_bad_launches() == 0, "%ld launches the stub refused", hipstub_bad_launches());
-    EXPECT(hipstub_live_allocs() == 0, "%ld device allocations alive at exit", hipstub_live_allocs());
-    std::printf("pg harness: %ld kernel launches, %d failures\n", hipstub_launches(), g_fail);
-    return g_fail ? 1 : 0;
+    return finish("pg harness", nullptr);
 }

@@ -7,17 +7,16 @@ under AddressSanitizer and UBSan."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO, load_golden
+import host_build
 import adapt_cases as cases
 import adapt_reference as ar
 
 WANT = ["lr_adapt_create", "lr_adapt_destroy", "lr_adapt_result", "lr_adapt_run", "lr_adapt_schedule", "lr_adapt_trace"]
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def _declared(header):
@@ -249,35 +248,9 @@ def test_both_warmups_keep_their_error_texts(pima, pscale):
         twin.uninstall()
 
 
-def test_host_side_of_the_warmup_under_asan_and_ubsan(tmp_path):
+def test_host_side_of_the_warmup_under_asan_and_ubsan():
     """tests/host/adapt_harness.cpp, a program of its own, linked with tests/host/hip_stub.cpp, lr_api.hip and the library's instantiation
-    objects exactly as tests/test_cov_cpu.py links the covariance harness."""
-    from logreg_amd import build as b
-    b.build(verbose=False)
-    cxx = os.path.join(LLVM, "clang++")
-    if not os.path.exists(cxx):
-        pytest.skip("ROCm's clang++ not found")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    host = ["-O1", "-g", "-std=c++17", *san]
-    inc = ["-I", os.path.join(REPO, "logreg_amd", "csrc"), "-I", os.path.join(REPO, "include")]
-    o = {k: str(tmp_path / f"{k}.o") for k in ("stub", "harness", "api")}
-    subprocess.run([cxx, *host, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-c", os.path.join(REPO, "tests", "host", "hip_stub.cpp"), "-o", o["stub"]],
-                   check=True, capture_output=True)
-    subprocess.run([cxx, *host, *inc, "-c", os.path.join(REPO, "tests", "host", "adapt_harness.cpp"), "-o", o["harness"]], check=True, capture_output=True)
-    xh = [a for f in san for a in ("-Xarch_host", f)]
-    r = subprocess.run([b._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *xh, *inc, '-DLR_BUILD_ID="sanitizer-harness"', "-c",
-                        os.path.join(REPO, "logreg_amd", "csrc", "lr_api.hip"), "-o", o["api"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    insts = [q for q in b.unit_objects() if os.path.basename(q).startswith("lr_inst_")]
-    assert len(insts) == 12
-    exe = str(tmp_path / "adapt_harness")
-    r = subprocess.run([cxx, *san, *o.values(), *insts, "-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    tail = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, tail
-    assert "ERROR: AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, tail
-    last = r.stdout.strip().splitlines()[-1]
-    assert last.startswith("adapt harness:") and last.endswith(" 0 failures"), tail
+    objects by tests/host_build.py."""
+    last = host_build.last_line(host_build.run(host_build.harness("adapt_harness.cpp")))
+    assert last.startswith("adapt harness:"), last
     assert int(last.split(":")[1].split("kernel launches")[0]) > 1000, last

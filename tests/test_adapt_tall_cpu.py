@@ -7,17 +7,16 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO, load_golden
+import host_build
 import adapt_reference as ar
 import adapt_tall_cases as cases
 
 WANT = ["lr_tall_adapt_create", "lr_tall_adapt_run"]
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def test_symbol_table_matches_the_header_and_both_libraries():
@@ -136,36 +135,9 @@ def test_nuts_warmup_stepwise_is_nuts_warmup_with_the_engine_as_data(pima, pscal
         twin.uninstall()
 
 
-def test_host_side_of_the_stepwise_warmup_under_asan_and_ubsan(tmp_path):
+def test_host_side_of_the_stepwise_warmup_under_asan_and_ubsan():
     """tests/host/adapt_tall_harness.cpp, a program of its own, linked with tests/host/hip_stub.cpp, lr_api.hip and the library's
-    instantiation objects exactly as tests/test_adapt_cpu.py links its harness."""
-    from logreg_amd import build as b
-    b.build(verbose=False)
-    cxx = os.path.join(LLVM, "clang++")
-    if not os.path.exists(cxx):
-        pytest.skip("ROCm's clang++ not found")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    host = ["-O1", "-g", "-std=c++17", *san]
-    inc = ["-I", os.path.join(REPO, "logreg_amd", "csrc"), "-I", os.path.join(REPO, "include")]
-    hip = ["-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include"]
-    o = {k: str(tmp_path / f"{k}.o") for k in ("stub", "harness", "api")}
-    subprocess.run([cxx, *host, *hip, "-c", os.path.join(REPO, "tests", "host", "hip_stub.cpp"), "-o", o["stub"]], check=True, capture_output=True)
-    r = subprocess.run([cxx, *host, *hip, *inc, "-Wno-unused-function", "-c", os.path.join(REPO, "tests", "host", "adapt_tall_harness.cpp"), "-o", o["harness"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    xh = [a for f in san for a in ("-Xarch_host", f)]
-    r = subprocess.run([b._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *xh, *inc, '-DLR_BUILD_ID="sanitizer-harness"', "-c",
-                        os.path.join(REPO, "logreg_amd", "csrc", "lr_api.hip"), "-o", o["api"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    insts = [q for q in b.unit_objects() if os.path.basename(q).startswith("lr_inst_")]
-    assert len(insts) == 12
-    exe = str(tmp_path / "adapt_tall_harness")
-    r = subprocess.run([cxx, *san, *o.values(), *insts, "-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    tail = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, tail
-    assert "ERROR: AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, tail
-    last = r.stdout.strip().splitlines()[-1]
-    assert last.startswith("adapt tall harness:") and last.endswith(" 0 failures"), tail
+    instantiation objects by tests/host_build.py."""
+    last = host_build.last_line(host_build.run(host_build.harness("adapt_tall_harness.cpp")))
+    assert last.startswith("adapt tall harness:"), last
     assert int(last.split(":")[1].split("kernel launches")[0]) > 1000, last

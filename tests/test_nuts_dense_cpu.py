@@ -7,18 +7,17 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+import host_build
 import nuts_dense_reference as dr
 import nuts_reference as nr
 
 WANT = ["lr_dense_adapt_create", "lr_dense_adapt_destroy", "lr_dense_adapt_result", "lr_dense_adapt_run", "lr_dense_adapt_trace", "lr_dense_factor",
         "lr_run_nuts_dense"]
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def _declared(header):
@@ -148,41 +147,14 @@ def test_still_13_units_and_the_dense_kernels_pass_the_gates_in_both_builds():
     b.resource_gate(strict=True, verbose=False)
 
 
-def test_host_side_under_asan_and_ubsan(tmp_path):
+def test_host_side_under_asan_and_ubsan():
     """tests/host/dense_harness.cpp, a program of its own, linked with tests/host/hip_stub.cpp, lr_api.hip and the library's
-    instantiation objects exactly as tests/test_adapt_cpu.py links the warm-up harness: the factorisation, lr_run_nuts_dense from host
+    instantiation objects by tests/host_build.py: the factorisation, lr_run_nuts_dense from host
     and device memory with the per-stream factor image, the planner's LDS arithmetic and refusal message (a float64 p = 20 model of 300
     rows: 81 600 bytes of rows + 81 920 of checkpoints at max_depth 10 fit the 163 840-byte budget, 16 384 bytes of matrices more do
     not), every refusal ahead of any device access, failing allocations, and the warm-up handle across its window ends."""
-    from logreg_amd import build as b
-    b.build(verbose=False)
-    cxx = os.path.join(LLVM, "clang++")
-    if not os.path.exists(cxx):
-        pytest.skip("ROCm's clang++ not found")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    host = ["-O1", "-g", "-std=c++17", *san]
-    inc = ["-I", os.path.join(REPO, "logreg_amd", "csrc"), "-I", os.path.join(REPO, "include")]
-    o = {k: str(tmp_path / f"{k}.o") for k in ("stub", "harness", "api")}
-    subprocess.run([cxx, *host, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-c", os.path.join(REPO, "tests", "host", "hip_stub.cpp"), "-o", o["stub"]],
-                   check=True, capture_output=True)
-    r = subprocess.run([cxx, *host, *inc, "-c", os.path.join(REPO, "tests", "host", "dense_harness.cpp"), "-o", o["harness"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    xh = [a for f in san for a in ("-Xarch_host", f)]
-    r = subprocess.run([b._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *xh, *inc, '-DLR_BUILD_ID="sanitizer-harness"', "-c",
-                        os.path.join(REPO, "logreg_amd", "csrc", "lr_api.hip"), "-o", o["api"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    insts = [q for q in b.unit_objects() if os.path.basename(q).startswith("lr_inst_")]
-    assert len(insts) == 12
-    exe = str(tmp_path / "dense_harness")
-    r = subprocess.run([cxx, *san, *o.values(), *insts, "-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    tail = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, tail
-    assert "ERROR: AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, tail
-    last = r.stdout.strip().splitlines()[-1]
-    assert last.startswith("dense harness:") and last.endswith(" 0 failures"), tail
+    last = host_build.last_line(host_build.run(host_build.harness("dense_harness.cpp")))
+    assert last.startswith("dense harness:"), last
     assert int(last.split(":")[1].split("kernel launches")[0]) > 1000, last
 
 

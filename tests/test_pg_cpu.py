@@ -6,17 +6,16 @@ run under AddressSanitizer and UBSan as a stand-alone program (tests/host/pg_har
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
+import host_build
 import pg_reference as pr
 import twin_pg
 
 WANT = ["lr_pg_omega", "lr_run_pg"]
-LLVM = "/opt/rocm/lib/llvm/bin"
 N_DRAWS = 400_000
 C64 = [0, 1e-8, 0.1, 1, 3.12, 3.13, 10, 40, 100, 1000]
 C32 = [0, 1e-8, 0.1, 1, 3.12, 3.13, 10, 40, 80]
@@ -252,37 +251,9 @@ def test_the_eight_kernels_pass_the_gates_in_both_builds():
     b.exec_prologue_gate(strict=True, verbose=False)
 
 
-def test_host_side_under_asan_and_ubsan(tmp_path):
+def test_host_side_under_asan_and_ubsan():
     """tests/host/pg_harness.cpp, a program of its own, linked with tests/host/hip_stub.cpp, lr_api.hip and the library's instantiation
-    objects exactly as tests/test_nuts_dense_cpu.py links the dense harness: the refusals, plan_pg and its reasons, the vector b, and
+    objects by tests/host_build.py: the refusals, plan_pg and its reasons, the vector b, and
     runs from host and device memory on the stub."""
-    from logreg_amd import build as b
-    b.build(verbose=False)
-    cxx = os.path.join(LLVM, "clang++")
-    if not os.path.exists(cxx):
-        pytest.skip("ROCm's clang++ not found")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    host = ["-O1", "-g", "-std=c++17", *san]
-    inc = ["-I", os.path.join(REPO, "logreg_amd", "csrc"), "-I", os.path.join(REPO, "include")]
-    o = {k: str(tmp_path / f"{k}.o") for k in ("stub", "harness", "api")}
-    subprocess.run([cxx, *host, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-c", os.path.join(REPO, "tests", "host", "hip_stub.cpp"), "-o", o["stub"]],
-                   check=True, capture_output=True)
-    r = subprocess.run([cxx, *host, *inc, "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-Wno-unused-function", "-c",
-                        os.path.join(REPO, "tests", "host", "pg_harness.cpp"), "-o", o["harness"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    xh = [a for f in san for a in ("-Xarch_host", f)]
-    r = subprocess.run([b._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *xh, *inc, '-DLR_BUILD_ID="sanitizer-harness"', "-c",
-                        os.path.join(REPO, "logreg_amd", "csrc", "lr_api.hip"), "-o", o["api"]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    insts = [q for q in b.unit_objects() if os.path.basename(q).startswith("lr_inst_")]
-    assert len(insts) == 12
-    exe = str(tmp_path / "pg_harness")
-    r = subprocess.run([cxx, *san, *o.values(), *insts, "-ldl", "-lpthread", "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    tail = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, tail
-    assert "ERROR: AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, tail
-    last = r.stdout.strip().splitlines()[-1]
-    assert last.startswith("pg harness:") and last.endswith(" 0 failures"), tail
+    last = host_build.last_line(host_build.run(host_build.harness("pg_harness.cpp")))
+    assert last.startswith("pg harness:"), last

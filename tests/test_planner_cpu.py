@@ -8,7 +8,7 @@ import subprocess
 
 import pytest
 
-from conftest import REPO
+import host_build
 from planner_cases import CASES, matches
 
 MODES = {0: "reg", 1: "lds", 2: "global", 3: "mfma", 4: "stepwise", 5: "mixed"}
@@ -19,20 +19,8 @@ PATHS = ("EXACT", "PER_STEP", "FUSED", "TRAJ")  # lr_plan.h InteriorPath
 
 
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    from logreg_amd import build as b
-    b.build(verbose=False)  # the instantiation objects the harness links against
-    out = tmp_path_factory.mktemp("plan_harness")
-    obj, exe = str(out / "plan_harness.o"), str(out / "plan_harness")
-    hipcc = b._hipcc()
-    inc = ["-I", os.path.join(REPO, "logreg_amd", "csrc"), "-I", os.path.join(REPO, "include")]
-    # host code under AddressSanitizer + UBSan (host side only: -Xarch_host; a finding aborts the harness and fails the test)
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *san, *inc, "-c", os.path.join(REPO, "tests", "host", "plan_harness.hip"),
-                    "-o", obj], check=True, capture_output=True)
-    objs = sorted(os.path.join(b.OBJDIR, f) for f in os.listdir(b.OBJDIR) if f.startswith("lr_inst_") and f.endswith(".o"))
-    assert len(objs) == 12
-    subprocess.run([hipcc, "--offload-arch=gfx950", *san[:2], obj, *objs, "-o", exe], check=True, capture_output=True)
+def harness():
+    exe = host_build.plan_harness()
 
     def ask(requests, cus=256):
         """requests: (dtype, p, n, chains, kind, precision, group, mode) -> plan dicts or ("ERR", text)"""

@@ -9,16 +9,13 @@ The trace does not see a launch's arguments (part_f32, fuse_mid, which buffer of
 compares the bytes that come out."""
 import difflib
 import os
-import subprocess
 
 from conftest import REPO
-from test_engine_sanitizers import _build
+import host_build
 
 
-def test_stepwise_launch_sequence_is_the_recorded_one(tmp_path):
-    exe = _build(tmp_path, [], "trace")
-    r = subprocess.run([exe, "trace"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+def test_stepwise_launch_sequence_is_the_recorded_one():
+    r = host_build.run(host_build.harness("engine_harness.cpp", "plain"), "trace")
     with open(os.path.join(REPO, "tests", "golden", "stepwise_launch_trace.txt")) as f:
         want = f.read().split("\n", 1)[1]  # (the first line names the commit the trace was recorded from)
     got = r.stdout
