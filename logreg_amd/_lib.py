@@ -213,6 +213,22 @@ PG_SYMBOLS = {
     "lr_pg_omega": (C.c_int, [_vp, _vp, _op, _vp]),
 }
 
+BRIDGE_ROWS = 12  # LR_BRIDGE_ROWS: logml, se, iterations, converged, N1, N2, n_eff used, non-finite terms, min / max of l1 and of l2
+BRIDGE_MAX_DRAWS = 1 << 20  # LR_BRIDGE_MAX_DRAWS
+BRIDGE_TAG = 0x08000000  # LR_BRIDGE_TAG
+# name -> (restype, argtypes); every symbol include/logreg_hip_bridge.h declares.  A table of its own like LOO_SYMBOLS, bound on first
+# use (load_bridge)
+BRIDGE_SYMBOLS = {
+    "lr_bridge_create": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _u64, C.POINTER(_vp)]),
+    "lr_bridge_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_bridge_terms": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "lr_bridge_proposal": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "lr_bridge_result": (C.c_int, [_vp, C.c_double, C.c_double, _i32, _vp]),
+    "lr_bridge_reset": (C.c_int, [_vp]),
+    "lr_bridge_destroy": (None, [_vp]),
+    "lr_bridge_solve": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, C.c_double, C.c_double, _i32, _i32, _vp, _vp]),
+}
+
 _lib = None
 _nuts = None
 _pg = None
@@ -222,6 +238,7 @@ _predict = None
 _acf = None
 _marg = None
 _loo = None
+_bridge = None
 _cov = None
 _adapt = None
 _adapt_tall = None
@@ -288,6 +305,16 @@ def bind_loo(L):
 def load_loo():
     """The library with the PSIS-LOO entry points bound (the same liblogreg_hip.so as load())."""
     return bind_loo(load())
+
+
+def bind_bridge(L):
+    """`L` (a loaded library handle) with the bridge-sampling entry points bound; resolved once per handle."""
+    return _bind(L, BRIDGE_SYMBOLS, "_bridge")
+
+
+def load_bridge():
+    """The library with the bridge-sampling entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_bridge(load())
 
 
 def bind_covariance(L):

@@ -23,6 +23,7 @@
 #include "../../include/logreg_hip_adapt_tall.h"
 #include "../../include/logreg_hip_dense.h"
 #include "../../include/logreg_hip_pg.h"
+#include "../../include/logreg_hip_bridge.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -53,6 +54,7 @@
 #include "lr_mfma.h"
 #include "lr_predict.h"
 #include "lr_loo.h"
+#include "lr_bridge.h"
 #include "lr_stats.h"
 #include "lr_tall.h"
 #include "lr_tall_nuts.h"
@@ -2018,6 +2020,273 @@ int lr_psis(int device, const void* loglik, int64_t S, int64_t r, int32_t dtype,
     LR_HIP(hipMemcpyAsync(table, dtab.p, (size_t)LR_LOO_ROWS * r * sizeof(double), hipMemcpyDeviceToHost, st));
     LR_HIP(hipStreamSynchronize(st));
     return LR_OK;
+}
+
+// ---- bridge sampling: the log marginal likelihood from the draws (include/logreg_hip_bridge.h; kernels: lr_bridge.h) -------------------
+}  // extern "C"
+struct lr_bridge : Staged {
+    lr_model* m = nullptr;
+    int device = 0;               // the model's (kept here: lr_bridge_destroy must not need the model)
+    int64_t cap = 0, N1 = 0, N2 = 0;
+    uint64_t seed = 0;
+    double cg = 0;                // -sum log L_ii - p / 2 log(2 pi)
+    double* d_prop = nullptr;     // mu [p] | inv_var [p] | W packed | L packed
+    double* d_l1 = nullptr;       // [cap]
+    double* d_l2 = nullptr;       // [N2]
+    double* d_iter = nullptr;     // the partials of a pass [blocks][3], then the state [BS_SLOTS]
+    Workspace part;               // row-slice partials of one chunk of draws
+    Workspace prop;               // a chunk of proposal draws [chunk][P]
+};
+namespace {
+static_assert(LR_BRIDGE_ROWS == lr::kBridgeRows && LR_BRIDGE_MAX_DRAWS == lr::kBridgeMaxDraws && LR_BRIDGE_TAG == lr::TAG_BRIDGE, "logreg_hip_bridge.h and lr_bridge.h");
+
+constexpr int64_t kBridgePropChunk = 1 << 16;  // proposal draws generated at a time
+int64_t bridge_blocks(int64_t N) { return (N + lr::kBridgeChunk - 1) / lr::kBridgeChunk; }
+int64_t bridge_row_slices(int64_t n) { return (n + lr::kBridgeSliceRows - 1) / lr::kBridgeSliceRows; }
+// draws whose row-slice partials are held at a time: 64 MB of them, at least 1024 draws
+int64_t bridge_chunk(int64_t n) { return std::max<int64_t>(1024, (int64_t)((size_t(64) << 20) / ((size_t)bridge_row_slices(n) * sizeof(double)))); }
+int bridge_reserve(lr_bridge* a, int64_t S) {
+    return a->part.grow((size_t)bridge_row_slices(a->m->n) * std::min(S, bridge_chunk(a->m->n)) * sizeof(double), "lr_bridge", "row-slice partials");
+}
+
+// the terms of S device-resident draws [S][P] -> d_out [S]; a->part holds a chunk (bridge_reserve)
+template <typename T, int P>
+int bridge_terms(lr_bridge* a, const void* d_draws, int64_t S, double* d_out, hipStream_t st) {
+    const lr_model* m = a->m;
+    const int64_t rsl = bridge_row_slices(m->n), chunk = bridge_chunk(m->n);
+    const int64_t want_blocks = (int64_t)(m->cus > 0 ? m->cus : 256) * 4;  // four waves on every SIMD, at least 64 draws a slice
+    for (int64_t c0 = 0; c0 < S; c0 += chunk) {
+        const int64_t cs = std::min(chunk, S - c0);
+        const int64_t sl = std::max<int64_t>(1, (want_blocks + rsl - 1) / rsl);
+        const int64_t per = std::max<int64_t>(64, (cs + sl - 1) / sl), dsl = (cs + per - 1) / per;
+        const T* d = static_cast<const T*>(d_draws) + c0 * P;
+        hipLaunchKernelGGL((lr::k_bridge_fill<T, P>), dim3((unsigned)rsl, (unsigned)dsl), dim3(lr::kBridgeBlock), 0, st, static_cast<const T*>(m->d_rows), m->n, d, cs,
+                           per, static_cast<double*>(a->part.p), cs);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL((lr::k_bridge_gauss<T, P>), dim3((unsigned)((cs + lr::kBridgeGaussBlock - 1) / lr::kBridgeGaussBlock)), dim3(lr::kBridgeGaussBlock), 0, st,
+                           d, cs, m->p, static_cast<const double*>(a->part.p), cs, rsl, static_cast<const double*>(a->d_prop), a->cg, m->lprior_const, d_out + c0);
+        LR_HIP(hipGetLastError());
+    }
+    return LR_OK;
+}
+int bridge_terms_any(lr_bridge* a, const void* d_draws, int64_t S, double* d_out, hipStream_t st) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, a->m->dtype, a->m->P, bridge_terms, a, d_draws, S, d_out, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_bridge: unsupported padded width %d", a->m->P);
+}
+
+// proposal draws [j0, j0 + cnt) -> a->prop [cnt][ldo], ldo = P or p
+template <typename T, int P>
+int bridge_propose(lr_bridge* a, int64_t j0, int64_t cnt, int ldo, hipStream_t st) {
+    hipLaunchKernelGGL((lr::k_bridge_propose<T, P>), dim3((unsigned)((cnt + lr::kBridgeGaussBlock - 1) / lr::kBridgeGaussBlock)), dim3(lr::kBridgeGaussBlock), 0, st,
+                       a->seed, j0, cnt, a->m->p, ldo, static_cast<const double*>(a->d_prop), static_cast<T*>(a->prop.p));
+    LR_HIP(hipGetLastError());
+    return LR_OK;
+}
+int bridge_propose_any(lr_bridge* a, int64_t j0, int64_t cnt, int ldo, hipStream_t st) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, a->m->dtype, a->m->P, bridge_propose, a, j0, cnt, ldo, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_bridge: unsupported padded width %d", a->m->P);
+}
+
+// The iteration and the error over device-resident terms -> table (host).  d_iter: 3 (blocks of N1 + blocks of N2) + BS_SLOTS doubles.
+// The host loops: it reads (log r, the previous log r) after every pass (lr_bridge.h says why).
+int bridge_solve(const double* d_l1, int64_t N1, const double* d_l2, int64_t N2, double n_eff, double tol, int maxit, double* d_iter, hipStream_t st,
+                 double* table) {
+    const int64_t nb1 = bridge_blocks(N1), nb2 = bridge_blocks(N2);
+    double* d_st = d_iter + 3 * (nb1 + nb2);
+    const double n1 = (double)N1, n2 = (double)N2, neff = n_eff > 0 && std::isfinite(n_eff) ? n_eff : n1;
+    const double s1 = neff / (neff + n2), s2 = n2 / (neff + n2), ls1 = std::log(s1), ls2 = std::log(s2);
+    const auto pass = [&](int mode) {
+        const int64_t blocks = mode == lr::BR_INIT ? nb2 : nb1 + nb2;
+        hipLaunchKernelGGL(lr::k_bridge_iterate, dim3((unsigned)blocks), dim3(lr::kBridgeBlock), 0, st, mode, d_l1, N1, d_l2, N2, nb2, ls1, ls2, s1, s2,
+                           static_cast<const double*>(d_st), d_iter);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(lr::k_bridge_finish, dim3(1), dim3(lr::kBridgeBlock), 0, st, mode, static_cast<const double*>(d_iter), nb1, nb2, n1, n2, neff, ls1, ls2,
+                           s1, s2, d_st);
+        LR_HIP(hipGetLastError());
+        return (int)LR_OK;
+    };
+    double h[lr::BS_SLOTS];
+    const auto read = [&](int count) {
+        LR_HIP(hipMemcpyAsync(h, d_st, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st));
+        LR_HIP(hipStreamSynchronize(st));
+        return (int)LR_OK;
+    };
+    fill_nan(table, LR_BRIDGE_ROWS);
+    if (const int rc = pass(lr::BR_SCAN)) return rc;
+    if (const int rc = read(lr::BS_SLOTS)) return rc;
+    table[2] = 0.0;
+    table[3] = 0.0;
+    table[4] = n1;
+    table[5] = n2;
+    table[6] = neff;
+    table[7] = h[lr::BS_BAD];
+    table[8] = h[lr::BS_MIN1];
+    table[9] = h[lr::BS_MAX1];
+    table[10] = h[lr::BS_MIN2];
+    table[11] = h[lr::BS_MAX2];
+    if (h[lr::BS_BAD] != 0.0) return LR_OK;  // a term that is not finite: logml and se stay NaN
+    if (const int rc = pass(lr::BR_INIT)) return rc;
+    int it = 0, conv = 0;
+    while (it < maxit && !conv) {
+        if (const int rc = pass(lr::BR_ITER)) return rc;
+        if (const int rc = read(2)) return rc;
+        ++it;
+        const double mag = std::fabs(h[lr::BS_LOGR]);
+        conv = std::fabs(h[lr::BS_LOGR] - h[lr::BS_PREV]) <= tol * (mag > 1.0 ? mag : 1.0);
+    }
+    if (const int rc = pass(lr::BR_ERR)) return rc;
+    if (const int rc = read(lr::BS_SLOTS)) return rc;
+    table[0] = h[lr::BS_LOGR];
+    table[1] = std::sqrt(h[lr::BS_RE2]);
+    table[2] = (double)it;
+    table[3] = (double)conv;
+    return LR_OK;
+}
+int bridge_check_solve(const char* who, double tol, int maxit) {
+    if (!(tol >= 0.0)) return fail(LR_ERR_INVALID, "%s: tol must be >= 0 (got %g)", who, tol);
+    if (maxit < 0) return fail(LR_ERR_INVALID, "%s: maxit must be >= 0 (got %d)", who, maxit);
+    return LR_OK;
+}
+}  // namespace
+extern "C" {
+
+int lr_bridge_create(lr_model* m, const double* mu, const double* cov, int64_t max_draws, int64_t n_proposal, uint64_t seed, lr_bridge** out) {
+    if (!m || !mu || !cov || !out) return fail(LR_ERR_INVALID, "lr_bridge_create: model / mu / cov / out is NULL");
+    if (max_draws <= 0 || n_proposal <= 0)
+        return fail(LR_ERR_INVALID, "lr_bridge_create: max_draws and n_proposal must be positive (got %lld, %lld)", (long long)max_draws, (long long)n_proposal);
+    if (max_draws > LR_BRIDGE_MAX_DRAWS || n_proposal > LR_BRIDGE_MAX_DRAWS)
+        return fail(LR_ERR_UNSUPPORTED, "lr_bridge_create: max_draws = %lld / n_proposal = %lld is beyond LR_BRIDGE_MAX_DRAWS = %d", (long long)max_draws,
+                    (long long)n_proposal, LR_BRIDGE_MAX_DRAWS);
+    if (bridge_row_slices(m->n) > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_bridge_create: n = %lld is beyond the launch grid", (long long)m->n);
+    const int p = m->p;
+    const size_t tri = (size_t)p * (p + 1) / 2;
+    std::vector<double> host(2 * (size_t)p + 2 * tri);
+    double cg = 0;
+    char why[160];
+    if (lr::bridge_factor(p, mu, cov, host.data() + 2 * p + tri, host.data() + 2 * p, &cg, why, sizeof(why))) return fail(LR_ERR_INVALID, "lr_bridge_create: %s", why);
+    std::copy(mu, mu + p, host.begin());
+    std::copy(m->inv_var, m->inv_var + p, host.begin() + p);
+    LR_HIP(hipSetDevice(m->device));
+    lr_bridge* a = new lr_bridge();
+    a->m = m;
+    a->device = m->device;
+    a->cap = max_draws;
+    a->N2 = n_proposal;
+    a->seed = seed;
+    a->cg = cg;
+    const int64_t pc = std::min(n_proposal, kBridgePropChunk);
+    const size_t iter_doubles = 3 * (size_t)(bridge_blocks(max_draws) + bridge_blocks(n_proposal)) + lr::BS_SLOTS;
+    int rc = upload("lr_bridge_create", "proposal", host.data(), host.size() * sizeof(double), (void**)&a->d_prop, LR_ERR_HIP);
+    if (!rc && (hipMalloc((void**)&a->d_l1, (size_t)max_draws * sizeof(double)) != hipSuccess || hipMalloc((void**)&a->d_l2, (size_t)n_proposal * sizeof(double)) != hipSuccess ||
+                hipMalloc((void**)&a->d_iter, iter_doubles * sizeof(double)) != hipSuccess))
+        rc = fail(LR_ERR_NOMEM, "lr_bridge_create: allocating the terms of %lld + %lld draws failed", (long long)max_draws, (long long)n_proposal);
+    if (!rc) rc = a->prop.grow((size_t)pc * m->P * m->esize(), "lr_bridge_create", "proposal draws");
+    if (!rc) rc = bridge_reserve(a, pc);
+    for (int64_t j0 = 0; !rc && j0 < n_proposal; j0 += pc) {  // the proposal terms, on the NULL stream
+        const int64_t cnt = std::min(pc, n_proposal - j0);
+        rc = bridge_propose_any(a, j0, cnt, m->P, nullptr);
+        if (!rc) rc = bridge_terms_any(a, a->prop.p, cnt, a->d_l2 + j0, nullptr);
+    }
+    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(LR_ERR_HIP, "lr_bridge_create: computing the proposal terms failed");
+    if (rc) {
+        lr_bridge_destroy(a);
+        return rc;
+    }
+    *out = a;
+    return LR_OK;
+}
+
+int lr_bridge_accumulate(lr_bridge* a, const void* draws, int64_t S, int32_t on_device, void* stream) {
+    if (!a || !draws) return fail(LR_ERR_INVALID, "lr_bridge_accumulate: accumulator / draws is NULL");
+    if (S <= 0) return fail(LR_ERR_INVALID, "lr_bridge_accumulate: S must be positive (got %lld)", (long long)S);
+    if (S > a->cap - a->N1)
+        return fail(LR_ERR_INVALID, "lr_bridge_accumulate: %lld draws held + %lld more exceed max_draws = %lld", (long long)a->N1, (long long)S, (long long)a->cap);
+    LR_HIP(hipSetDevice(a->device));
+    return stage_draws(
+        "lr_bridge", *a, a->m, Feed{draws, S, on_device != 0, (hipStream_t)stream}, [a](int64_t S0) { return bridge_reserve(a, S0); },
+        [a](const void* d_draws, int64_t Sb, hipStream_t st) {
+            if (const int rc = bridge_terms_any(a, d_draws, Sb, a->d_l1 + a->N1, st)) return rc;
+            a->N1 += Sb;
+            return (int)LR_OK;
+        });
+}
+
+int lr_bridge_terms(lr_bridge* a, double* l1, double* l2, int64_t* n1, int64_t* n2) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_bridge_terms: accumulator is NULL");
+    if (n1) *n1 = a->N1;
+    if (n2) *n2 = a->N2;
+    LR_HIP(hipSetDevice(a->device));
+    if (l1 && a->N1 > 0) LR_HIP(hipMemcpyAsync(l1, a->d_l1, (size_t)a->N1 * sizeof(double), hipMemcpyDeviceToHost, a->last));
+    if (l2) LR_HIP(hipMemcpyAsync(l2, a->d_l2, (size_t)a->N2 * sizeof(double), hipMemcpyDeviceToHost, a->last));
+    LR_HIP(hipStreamSynchronize(a->last));
+    return LR_OK;
+}
+
+int lr_bridge_proposal(lr_bridge* a, void* host_out, int64_t* n2) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_bridge_proposal: accumulator is NULL");
+    if (n2) *n2 = a->N2;
+    if (!host_out) return LR_OK;
+    LR_HIP(hipSetDevice(a->device));
+    const lr_model* m = a->m;
+    const int64_t pc = std::min(a->N2, kBridgePropChunk);
+    const size_t es = m->esize();
+    LR_HIP(hipStreamSynchronize(a->last));  // a->prop is about to be overwritten
+    for (int64_t j0 = 0; j0 < a->N2; j0 += pc) {
+        const int64_t cnt = std::min(pc, a->N2 - j0);
+        if (const int rc = bridge_propose_any(a, j0, cnt, m->p, a->last)) return rc;
+        LR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(host_out) + (size_t)j0 * m->p * es, a->prop.p, (size_t)cnt * m->p * es, hipMemcpyDeviceToHost, a->last));
+        LR_HIP(hipStreamSynchronize(a->last));
+    }
+    return LR_OK;
+}
+
+int lr_bridge_result(lr_bridge* a, double n_eff, double tol, int32_t maxit, double* table) {
+    if (!a || !table) return fail(LR_ERR_INVALID, "lr_bridge_result: accumulator / table is NULL");
+    if (const int rc = bridge_check_solve("lr_bridge_result", tol, maxit)) return rc;
+    if (a->N1 == 0) {
+        fill_nan(table, LR_BRIDGE_ROWS);
+        table[2] = table[3] = table[4] = 0.0;
+        table[5] = (double)a->N2;
+        return LR_OK;
+    }
+    LR_HIP(hipSetDevice(a->device));
+    return bridge_solve(a->d_l1, a->N1, a->d_l2, a->N2, n_eff, tol, maxit, a->d_iter, a->last, table);
+}
+
+int lr_bridge_reset(lr_bridge* a) {
+    if (!a) return fail(LR_ERR_INVALID, "lr_bridge_reset: accumulator is NULL");
+    a->N1 = 0;  // the next draws overwrite the posterior terms from the first; the proposal terms stay
+    return LR_OK;
+}
+
+void lr_bridge_destroy(lr_bridge* a) {
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    free_all({a->d_prop, a->d_l1, a->d_l2, a->d_iter, a->part.p, a->prop.p, a->in.p, a->padded.p});
+    delete a;
+}
+
+int lr_bridge_solve(int device, const double* l1, int64_t N1, const double* l2, int64_t N2, double n_eff, double tol, int32_t maxit, int32_t on_device,
+                    double* table, void* stream) {
+    if (!l1 || !l2 || !table) return fail(LR_ERR_INVALID, "lr_bridge_solve: l1 / l2 / table is NULL");
+    if (N1 <= 0 || N2 <= 0) return fail(LR_ERR_INVALID, "lr_bridge_solve: N1 and N2 must be positive (got %lld, %lld)", (long long)N1, (long long)N2);
+    if (const int rc = bridge_check_solve("lr_bridge_solve", tol, maxit)) return rc;
+    if (N1 > 0x7FFFFFFFll || N2 > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_bridge_solve: N1 = %lld / N2 = %lld is beyond 2^31 - 1", (long long)N1, (long long)N2);
+    if (const int rc = use_device(device, "lr_bridge_solve", true)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DevBuf d1, d2, dit;
+    if ((!on_device && (d1.alloc((size_t)N1 * sizeof(double)) || d2.alloc((size_t)N2 * sizeof(double)))) ||
+        dit.alloc((3 * (size_t)(bridge_blocks(N1) + bridge_blocks(N2)) + lr::BS_SLOTS) * sizeof(double)))
+        return fail(LR_ERR_NOMEM, "lr_bridge_solve: allocating the workspaces of %lld + %lld terms failed", (long long)N1, (long long)N2);
+    if (!on_device) {
+        LR_HIP(hipMemcpyAsync(d1.p, l1, (size_t)N1 * sizeof(double), hipMemcpyHostToDevice, st));
+        LR_HIP(hipMemcpyAsync(d2.p, l2, (size_t)N2 * sizeof(double), hipMemcpyHostToDevice, st));
+        l1 = static_cast<const double*>(d1.p);
+        l2 = static_cast<const double*>(d2.p);
+    }
+    const int rc = bridge_solve(l1, N1, l2, N2, n_eff, tol, maxit, static_cast<double*>(dit.p), st, table);
+    (void)hipStreamSynchronize(st);  // the workspaces are freed on return
+    return rc;
 }
 
 // ---- device memory / stream / event helpers -------------------------------------------------------
