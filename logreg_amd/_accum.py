@@ -1,6 +1,6 @@
 """What the accumulators of kept draws share on the Python face (the host scaffold under them is csrc/lr_accum.h).
 
-`BlockAccumulator`   `Autocorr`, `Marginals`, `Covariance`: blocks `[k, C, p]` in time order, created on a device at the first `update`, freed by `free`
+`BlockAccumulator`   `Autocorr`, `Marginals`, `Covariance`, `RankDiagnostics` (which stores its blocks, and so also checks for room): blocks `[k, C, p]` in time order, created on a device at the first `update`, freed by `free`
 `ModelAccumulator`   `PosteriorPredictive`, `PsisLoo`: draws `[S, p]` of a `LogReg`, created with the model, closed by `close`
 
 A subclass names its entry points (`_prefix`: `<prefix>_accumulate`, `_reset`, `_destroy` of the C ABI) and supplies what really differs:

@@ -229,6 +229,20 @@ BRIDGE_SYMBOLS = {
     "lr_bridge_solve": (C.c_int, [C.c_int, _vp, _i64, _vp, _i64, C.c_double, C.c_double, _i32, _i32, _vp, _vp]),
 }
 
+RANK_MAX_LAG = 255  # LR_RANK_MAX_LAG
+RANK_MAX_DRAWS = 1 << 24  # LR_RANK_MAX_DRAWS: draws per coordinate, chains x max_steps
+RANK_ROWS = 15  # LR_RANK_ROWS
+# name -> (restype, argtypes); every symbol include/logreg_hip_rank.h declares.  A table of its own like ACF_SYMBOLS, bound on first use
+# (load_rank)
+RANK_SYMBOLS = {
+    "lr_rank_create": (C.c_int, [C.c_int, _i32, _i64, _i32, _i64, _i32, C.POINTER(_vp)]),
+    "lr_rank_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_rank_result": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "lr_rank_ranks": (C.c_int, [_vp, _i32, _i32, _vp, _vp, C.POINTER(_i64)]),
+    "lr_rank_reset": (C.c_int, [_vp]),
+    "lr_rank_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _pg = None
@@ -239,6 +253,7 @@ _acf = None
 _marg = None
 _loo = None
 _bridge = None
+_rank = None
 _cov = None
 _adapt = None
 _adapt_tall = None
@@ -315,6 +330,16 @@ def bind_bridge(L):
 def load_bridge():
     """The library with the bridge-sampling entry points bound (the same liblogreg_hip.so as load())."""
     return bind_bridge(load())
+
+
+def bind_rank(L):
+    """`L` (a loaded library handle) with the rank-diagnostics entry points bound; resolved once per handle."""
+    return _bind(L, RANK_SYMBOLS, "_rank")
+
+
+def load_rank():
+    """The library with the rank-diagnostics entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_rank(load())
 
 
 def bind_covariance(L):

@@ -24,6 +24,7 @@
 #include "../../include/logreg_hip_dense.h"
 #include "../../include/logreg_hip_pg.h"
 #include "../../include/logreg_hip_bridge.h"
+#include "../../include/logreg_hip_rank.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -55,6 +56,7 @@
 #include "lr_predict.h"
 #include "lr_loo.h"
 #include "lr_bridge.h"
+#include "lr_rank.h"
 #include "lr_stats.h"
 #include "lr_tall.h"
 #include "lr_tall_nuts.h"
@@ -1087,6 +1089,251 @@ void lr_acf_destroy(lr_acf* a) {
     (void)hipSetDevice(a->device);
     free_all({a->d_state, a->in.p, a->ws.p});
     delete a;
+}
+
+// ---- rank-normalised split-R-hat, bulk and tail ESS of stored draws (include/logreg_hip_rank.h; kernels: lr_rank.h) ---------------------
+}  // extern "C"
+struct lr_rank : Staged {
+    int device = 0;
+    int dtype = LR_F32;
+    int64_t C = 0, max_steps = 0;
+    int p = 0, K = 0;
+    int64_t n = 0;             // time steps stored
+    void* d_store = nullptr;   // X [max_steps][C][p] in the draws' dtype
+    Workspace ws;              // everything a result needs, for one batch of coordinates
+    size_t esize() const { return dtype == LR_F32 ? 4 : 8; }
+    size_t row() const { return (size_t)C * p * esize(); }
+};
+namespace {
+static_assert(LR_RANK_MAX_LAG == lr::kRankMaxLag, "largest lag");
+static_assert(LR_RANK_MAX_DRAWS / 2 <= 0x7FFFFFFFll, "a split chain per workgroup of the launch grid");
+
+// How one batch of pb coordinates is laid out in the workspace (in 8-byte words), for n stored steps.
+struct RankPlan {
+    int64_t h, S, N, M, nblk;
+    int L, rows, pb;
+    size_t K, U, R, V, A, part, tab, Q, z, words;
+    RankPlan(const lr_rank* r, int pb_, bool ranks) : pb(pb_) {
+        h = r->n / 2;
+        M = 2 * r->C;
+        S = h * M;
+        N = 2;
+        while (N < S) N <<= 1;
+        L = (int)std::min<int64_t>(r->K, h - 1);
+        rows = L + 1 + LR_RANK_TAB_HEAD;
+        nblk = (M + 255) / 256;
+        size_t o = 0;
+        const auto take = [&o](size_t w) { const size_t at = o; o += w; return at; };
+        K = take((size_t)pb * N);
+        U = take((size_t)pb * S);
+        R = take((size_t)pb * S);
+        V = take((size_t)lr::kRankSeries * pb * S);
+        A = take((size_t)lr::kRankSeries * pb * (L + 2) * M);
+        part = take((size_t)lr::kRankSeries * pb * rows * nblk);
+        tab = take((size_t)lr::kRankSeries * pb * rows);
+        Q = take((size_t)pb * lr::kRankQ);
+        z = take(ranks ? (size_t)S : 0);
+        words = o;
+    }
+};
+// the most one batch of coordinates may take of device memory, and of the launch grid
+constexpr size_t kRankBatchBytes = size_t(1) << 30;
+constexpr int kRankBatchMax = 4096;
+
+int rank_sort(uint64_t* K, int64_t N, int pb, hipStream_t st) {
+    const unsigned tiles = (unsigned)std::max<int64_t>(1, N / lr::kRankTile);
+    hipLaunchKernelGGL(lr::k_rank_sort_tile, dim3(tiles, pb), dim3(lr::kRankSortBlock), 0, st, K, N, (int64_t)0);
+    LR_HIP(hipGetLastError());
+    for (int64_t k = 2 * (int64_t)lr::kRankTile; k <= N; k <<= 1) {
+        for (int64_t j = k >> 1; j >= lr::kRankTile; j >>= 1) {
+            hipLaunchKernelGGL(lr::k_rank_merge_global, dim3((unsigned)((N / 2 + 255) / 256), pb), dim3(256), 0, st, K, N, k, j);
+            LR_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(lr::k_rank_sort_tile, dim3(tiles, pb), dim3(lr::kRankSortBlock), 0, st, K, N, k);
+        LR_HIP(hipGetLastError());
+    }
+    return LR_OK;
+}
+
+// Enqueue, for coordinates j0 .. j0 + pb of the stored draws: keys, sort, quantiles, and the passes `plain` / `fold` ask for (2r into R,
+// z into V; the later pass overwrites R; z in time order where z_out is given).
+template <typename T>
+int rank_order(lr_rank* r, const RankPlan& P, int j0, bool plain, bool fold, double* z_out, hipStream_t st) {
+    uint64_t* w = static_cast<uint64_t*>(r->ws.p);
+    double* V = reinterpret_cast<double*>(w + P.V);
+    int64_t* R = reinterpret_cast<int64_t*>(w + P.R);
+    const dim3 gN((unsigned)((P.N + 255) / 256), P.pb), gS((unsigned)((P.S + 255) / 256), P.pb);
+    hipLaunchKernelGGL(lr::k_rank_gather<T>, gN, dim3(256), 0, st, static_cast<const T*>(r->d_store), r->p, j0, P.S, P.N, w + P.U, w + P.K);
+    LR_HIP(hipGetLastError());
+    if (const int rc = rank_sort(w + P.K, P.N, P.pb, st)) return rc;
+    hipLaunchKernelGGL(lr::k_rank_quant, dim3((unsigned)((P.pb + 63) / 64)), dim3(64), 0, st, w + P.K, P.S, P.N, P.pb, w + P.Q);
+    LR_HIP(hipGetLastError());
+    if (plain) {
+        hipLaunchKernelGGL(lr::k_rank_lookup<false>, gS, dim3(256), 0, st, w + P.U, w + P.K, w + P.Q, P.S, P.N, R);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(lr::k_rank_transform<false>, gS, dim3(256), 0, st, w + P.U, R, w + P.Q, r->C, 2 * P.h, P.S, V, fold ? nullptr : z_out);
+        LR_HIP(hipGetLastError());
+    }
+    if (fold) {
+        hipLaunchKernelGGL(lr::k_rank_fold, gN, dim3(256), 0, st, w + P.U, w + P.Q, P.S, P.N, w + P.K);
+        LR_HIP(hipGetLastError());
+        if (const int rc = rank_sort(w + P.K, P.N, P.pb, st)) return rc;
+        hipLaunchKernelGGL(lr::k_rank_lookup<true>, gS, dim3(256), 0, st, w + P.U, w + P.K, w + P.Q, P.S, P.N, R);
+        LR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(lr::k_rank_transform<true>, gS, dim3(256), 0, st, w + P.U, R, w + P.Q, r->C, 2 * P.h, P.S, V, z_out);
+        LR_HIP(hipGetLastError());
+    }
+    return LR_OK;
+}
+
+template <typename T>
+int rank_batch(lr_rank* r, const RankPlan& P, int j0, double* h_tab, uint64_t* h_Q, hipStream_t st) {
+    if (const int rc = rank_order<T>(r, P, j0, true, true, nullptr, st)) return rc;
+    uint64_t* w = static_cast<uint64_t*>(r->ws.p);
+    double* V = reinterpret_cast<double*>(w + P.V);
+    double* A = reinterpret_cast<double*>(w + P.A);
+    double* part = reinterpret_cast<double*>(w + P.part);
+    double* tab = reinterpret_cast<double*>(w + P.tab);
+    const int series = lr::kRankSeries * P.pb;
+    const int64_t cells = (int64_t)series * P.rows;
+    hipLaunchKernelGGL(lr::k_rank_lag, dim3((unsigned)P.M, series), dim3(256), 0, st, V, P.h, P.M, P.pb, P.L, A);
+    LR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lr::k_rank_partial, dim3((unsigned)P.nblk, P.rows, series), dim3(256), 0, st, A, P.M, part);
+    LR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lr::k_rank_final, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, part, P.nblk, cells, tab);
+    LR_HIP(hipGetLastError());
+    LR_HIP(hipMemcpyAsync(h_tab, tab, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipMemcpyAsync(h_Q, w + P.Q, (size_t)P.pb * lr::kRankQ * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+// rows of the result table of one coordinate, from its four series' tables and its quantiles
+void rank_finish(const lr_rank* r, const RankPlan& P, const double* tab, const uint64_t* Q, int jb, int j, double* table) {
+    const int p = r->p;
+    const auto cell = [&](int row) -> double& { return table[(size_t)row * p + j]; };
+    for (int row = 0; row < LR_RANK_ROWS; ++row) cell(row) = (double)NAN;
+    const uint64_t* q = Q + (size_t)jb * lr::kRankQ;
+    cell(11) = (double)q[3];
+    if (q[3]) return;  // a NaN or an infinity among the draws
+    for (int i = 0; i < 3; ++i) std::memcpy(&cell(8 + i), &q[i], sizeof(double));
+    double rhat[4], ess[4], capped[4], pairs[4];
+    for (int s = 0; s < lr::kRankSeries; ++s)
+        lr_rank_series(tab + ((size_t)s * P.pb + jb) * P.rows, P.h, P.M, s == 1 ? 0 : P.L, r->K, s != 1, &rhat[s], &ess[s], &capped[s], &pairs[s]);
+    cell(0) = rhat[0];
+    cell(1) = rhat[1];
+    cell(2) = std::isnan(rhat[0]) || std::isnan(rhat[1]) ? (double)NAN : std::max(rhat[0], rhat[1]);
+    cell(3) = ess[0];
+    cell(4) = std::isnan(ess[2]) || std::isnan(ess[3]) ? (double)NAN : std::min(ess[2], ess[3]);
+    for (int i = 0; i < 3; ++i) {
+        cell(5 + i) = capped[i ? i + 1 : 0];
+        cell(12 + i) = pairs[i ? i + 1 : 0];
+    }
+}
+}  // namespace
+extern "C" {
+
+int lr_rank_create(int device, int32_t dtype, int64_t C, int32_t p, int64_t max_steps, int32_t max_lag, lr_rank** out) {
+    if (!out) return fail(LR_ERR_INVALID, "lr_rank_create: out is NULL");
+    if (C <= 0 || p <= 0 || max_steps <= 0)
+        return fail(LR_ERR_INVALID, "lr_rank_create: C, p and max_steps must be positive (got %lld, %d, %lld)", (long long)C, p, (long long)max_steps);
+    if (max_lag < 1 || max_lag > LR_RANK_MAX_LAG || max_lag % 2 == 0)
+        return fail(LR_ERR_INVALID, "lr_rank_create: max_lag must be odd and in 1..%d (got %d)", LR_RANK_MAX_LAG, max_lag);
+    if (dtype != LR_F32 && dtype != LR_F64) return fail(LR_ERR_INVALID, "lr_rank_create: dtype must be LR_F32 or LR_F64");
+    if (C > LR_RANK_MAX_DRAWS || max_steps > LR_RANK_MAX_DRAWS / C)
+        return fail(LR_ERR_UNSUPPORTED, "lr_rank_create: %lld chains x %lld steps are more than the cap of %lld draws per coordinate (LR_RANK_MAX_DRAWS)",
+                    (long long)C, (long long)max_steps, (long long)LR_RANK_MAX_DRAWS);
+    if (const int rc = use_device(device, "lr_rank_create")) return rc;
+    lr_rank* r = new lr_rank();
+    r->device = device;
+    r->dtype = dtype;
+    r->C = C;
+    r->p = p;
+    r->K = max_lag;
+    r->max_steps = max_steps;
+    const size_t want = (size_t)max_steps * r->row();
+    if (hipMalloc(&r->d_store, want) != hipSuccess) {
+        delete r;
+        return fail(LR_ERR_NOMEM, "lr_rank_create: allocating %zu bytes for the draws failed", want);
+    }
+    *out = r;
+    return LR_OK;
+}
+
+int lr_rank_accumulate(lr_rank* r, const void* block, int64_t k, int32_t on_device, void* stream) {
+    if (!r || !block) return fail(LR_ERR_INVALID, "lr_rank_accumulate: accumulator / block is NULL");
+    if (k <= 0) return fail(LR_ERR_INVALID, "lr_rank_accumulate: k must be positive (got %lld)", (long long)k);
+    if (k > r->max_steps - r->n)
+        return fail(LR_ERR_INVALID, "lr_rank_accumulate: %lld more steps after %lld exceed max_steps = %lld", (long long)k, (long long)r->n, (long long)r->max_steps);
+    LR_HIP(hipSetDevice(r->device));
+    return stage_block("lr_rank", *r, r->row(), Feed{block, k, on_device != 0, (hipStream_t)stream}, [r](const void* d_block, int64_t kb, hipStream_t st) {
+        LR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(r->d_store) + (size_t)r->n * r->row(), d_block, (size_t)kb * r->row(), hipMemcpyDeviceToDevice, st));
+        r->n += kb;
+        return (int)LR_OK;
+    });
+}
+
+int lr_rank_result(lr_rank* r, double* table, int64_t* n_draws) {
+    if (!r || !table) return fail(LR_ERR_INVALID, "lr_rank_result: accumulator / table is NULL");
+    LR_HIP(hipSetDevice(r->device));
+    if (n_draws) *n_draws = r->n;
+    fill_nan(table, (size_t)LR_RANK_ROWS * r->p);
+    if (r->n < 4) {
+        std::fill(table + (size_t)11 * r->p, table + (size_t)12 * r->p, 0.0);
+        return LR_OK;
+    }
+    const size_t per = RankPlan(r, 1, false).words * sizeof(uint64_t);
+    const int pb = (int)std::max<size_t>(1, std::min<size_t>({(size_t)r->p, (size_t)kRankBatchMax, kRankBatchBytes / per}));
+    const RankPlan P(r, pb, false);
+    if (const int rc = r->ws.grow(P.words * sizeof(uint64_t), "lr_rank", "result workspace")) return rc;
+    std::vector<double> h_tab;
+    std::vector<uint64_t> h_Q;
+    try {
+        h_tab.resize((size_t)lr::kRankSeries * pb * P.rows);
+        h_Q.resize((size_t)pb * lr::kRankQ);
+    } catch (const std::bad_alloc&) {
+        return fail(LR_ERR_NOMEM, "lr_rank_result: allocating the host tables failed");
+    }
+    for (int j0 = 0; j0 < r->p; j0 += pb) {
+        // (a last batch of fewer coordinates runs as a full one on coordinates that end at p: the layout stays P's)
+        const int jf = std::min(j0, r->p - pb);
+        if (const int rc = LR_BY_DTYPE(r->dtype, rank_batch, r, P, jf, h_tab.data(), h_Q.data(), r->last)) return rc;
+        for (int j = j0; j < std::min(r->p, j0 + pb); ++j) rank_finish(r, P, h_tab.data(), h_Q.data(), j - jf, j, table);
+    }
+    return LR_OK;
+}
+
+int lr_rank_ranks(lr_rank* r, int32_t j, int32_t folded, int64_t* twice_r, double* z, int64_t* n_used) {
+    if (!r || !twice_r) return fail(LR_ERR_INVALID, "lr_rank_ranks: accumulator / twice_r is NULL");
+    if (j < 0 || j >= r->p) return fail(LR_ERR_INVALID, "lr_rank_ranks: coordinate %d is not in 0..%d", j, r->p - 1);
+    LR_HIP(hipSetDevice(r->device));
+    if (n_used) *n_used = r->n / 2 * 2;
+    if (r->n < 2) return LR_OK;
+    const RankPlan P(r, 1, true);
+    if (const int rc = r->ws.grow(P.words * sizeof(uint64_t), "lr_rank", "ranks workspace")) return rc;
+    uint64_t* w = static_cast<uint64_t*>(r->ws.p);
+    hipStream_t st = r->last;
+    if (const int rc = LR_BY_DTYPE(r->dtype, rank_order, r, P, (int)j, !folded, folded != 0, z ? reinterpret_cast<double*>(w + P.z) : nullptr, st))
+        return rc;
+    LR_HIP(hipMemcpyAsync(twice_r, w + P.R, (size_t)P.S * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (z) LR_HIP(hipMemcpyAsync(z, w + P.z, (size_t)P.S * sizeof(double), hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_rank_reset(lr_rank* r) {
+    if (!r) return fail(LR_ERR_INVALID, "lr_rank_reset: accumulator is NULL");
+    LR_HIP(hipSetDevice(r->device));
+    LR_HIP(hipStreamSynchronize(r->last));
+    r->n = 0;
+    return LR_OK;
+}
+
+void lr_rank_destroy(lr_rank* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    free_all({r->d_store, r->in.p, r->ws.p});
+    delete r;
 }
 
 // ---- marginal histograms, min / max and power sums of the kept draws (include/logreg_hip_marginals.h; kernels: lr_marginals.h) ---------

@@ -699,6 +699,9 @@ def _accumulator_class(keyword):
     if keyword == "autocorr":
         from .autocorr import Autocorr
         return Autocorr, "an Autocorr"
+    if keyword == "rank":
+        from .rankdiag import RankDiagnostics
+        return RankDiagnostics, "a RankDiagnostics"
     if keyword == "marginals":
         from .marginals import Marginals
         return Marginals, "a Marginals"
@@ -714,7 +717,7 @@ def _accumulator_class(keyword):
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
-         autocorr=None, loo=None, bridge=None, covariance=None, marginals=None, predictive=None):
+         autocorr=None, rank=None, loo=None, bridge=None, covariance=None, marginals=None, predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -745,6 +748,10 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     it on the device, in time order, before the block is copied or freed (under `summary_only=True` the block lives only that long);
     the summary dict -- or, with `return_info=True`, the info dict -- gains `"autocorr": autocorr.result()` (Geyer ESS per chain and
     pooled, the pooled autocorrelation).  Chains, states, statistics and accept counts are those of the same call without it.
+    `rank` (fused kernels): a `RankDiagnostics` of the run's chain count, p, dtype and device with room for `iters` more steps.  Every
+    chunk's block of kept samples is stored in it on the device exactly where `autocorr` is fed; the summary dict -- or, with
+    `return_info=True`, the info dict -- gains `"rank": rank.result()` (rank-normalised split-R-hat, bulk and tail ESS, exact median and
+    5 % / 95 % order statistics).  Chains, states, statistics and accept counts are those of the same call without it.
     `marginals` (fused kernels): a `Marginals` of the run's chain count, p, dtype and device.  Every chunk's block of kept samples is
     folded into it on the device exactly where `autocorr` is; the summary dict -- or, with `return_info=True`, the info dict -- gains
     `"marginals": marginals.result()` (min/max, mean, variance, skewness, kurtosis, the histograms; `quantile`, `interval` and `hpd` of
@@ -771,10 +778,10 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     a larger run passes the whole run's: its chains then run on the variants they have in the whole run, bit for bit).
     """
     # the accumulators given: refused in the order of the keywords here, fed and reported in the order of `accs`
-    given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("marginals", marginals), ("covariance", covariance), ("loo", loo),
+    given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("rank", rank), ("marginals", marginals), ("covariance", covariance), ("loo", loo),
                                               ("bridge", bridge))
              if acc is not None}
-    accs = [(name, given[name]) for name in ("autocorr", "marginals", "covariance", "loo", "bridge", "predictive") if name in given]
+    accs = [(name, given[name]) for name in ("autocorr", "rank", "marginals", "covariance", "loo", "bridge", "predictive") if name in given]
     if not isinstance(kernel, FusedKernel):
         for name in given:
             raise ValueError(f"{name}= needs a fused kernel (the closures of a LogReg)")
