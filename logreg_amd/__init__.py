@@ -26,6 +26,7 @@ from .optimize import find_map, laplace_metric, overdispersed_init  # noqa: F401
 from .predict import PosteriorPredictive, merge_predictive, predict_proba, waic, waic_from_table  # noqa: F401
 from .loo import PsisLoo, loo_compare, loo_from_table, psis_from_loglik, psis_loo  # noqa: F401
 from .rankdiag import RankDiagnostics, rank_result_from_table  # noqa: F401
+from .ppc import PredictiveCheck, ppc_from_table  # noqa: F401
 from .bridge import Bridge, bridge_compare, bridge_from_table, bridge_from_terms, bridge_proposal, bridge_sampling  # noqa: F401
 from .output import print_summary, read_parquet, to_frame, write_parquet  # noqa: F401
 
@@ -34,4 +35,4 @@ __all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "mala
            "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "laplace_metric", "overdispersed_init", "write_parquet",
            "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals", "Covariance", "covariance_scaling", "merge_covariance",
            "nuts_warmup", "nuts_warmup_dense", "nuts_warmup_stepwise", "PsisLoo", "psis_loo", "psis_from_loglik", "loo_from_table", "loo_compare",
-           "RankDiagnostics", "rank_result_from_table", "Bridge", "bridge_sampling", "bridge_from_terms", "bridge_from_table", "bridge_compare", "bridge_proposal"]
+           "RankDiagnostics", "rank_result_from_table", "PredictiveCheck", "ppc_from_table", "Bridge", "bridge_sampling", "bridge_from_terms", "bridge_from_table", "bridge_compare", "bridge_proposal"]

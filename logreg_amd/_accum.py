@@ -1,7 +1,7 @@
 """What the accumulators of kept draws share on the Python face (the host scaffold under them is csrc/lr_accum.h).
 
 `BlockAccumulator`   `Autocorr`, `Marginals`, `Covariance`, `RankDiagnostics` (which stores its blocks, and so also checks for room): blocks `[k, C, p]` in time order, created on a device at the first `update`, freed by `free`
-`ModelAccumulator`   `PosteriorPredictive`, `PsisLoo`: draws `[S, p]` of a `LogReg`, created with the model, closed by `close`
+`ModelAccumulator`   `PosteriorPredictive`, `PsisLoo`, `Bridge`, `PredictiveCheck`: draws `[S, p]` of a `LogReg`, created with the model, closed by `close`
 
 A subclass names its entry points (`_prefix`: `<prefix>_accumulate`, `_reset`, `_destroy` of the C ABI) and supplies what really differs:
 its constructor's own checks, the create call and the results.  `mcmc` asks every accumulator it is given `check_run` before anything runs.

@@ -243,6 +243,20 @@ RANK_SYMBOLS = {
     "lr_rank_destroy": (None, [_vp]),
 }
 
+PPC_MAX_GROUPS = 32  # LR_PPC_MAX_GROUPS
+PPC_TAG = 0x04000000  # LR_PPC_TAG
+PPC_MOMENTS = 4  # LR_PPC_MOMENTS
+# name -> (restype, argtypes); every symbol include/logreg_hip_ppc.h declares.  A table of its own like PREDICT_SYMBOLS, bound on first
+# use (load_ppc)
+PPC_SYMBOLS = {
+    "lr_ppc_create": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _u64, C.POINTER(_vp)]),
+    "lr_ppc_accumulate": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "lr_ppc_result": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "lr_ppc_terms": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "lr_ppc_reset": (C.c_int, [_vp]),
+    "lr_ppc_destroy": (None, [_vp]),
+}
+
 _lib = None
 _nuts = None
 _pg = None
@@ -254,6 +268,7 @@ _marg = None
 _loo = None
 _bridge = None
 _rank = None
+_ppc = None
 _cov = None
 _adapt = None
 _adapt_tall = None
@@ -340,6 +355,16 @@ def bind_rank(L):
 def load_rank():
     """The library with the rank-diagnostics entry points bound (the same liblogreg_hip.so as load())."""
     return bind_rank(load())
+
+
+def bind_ppc(L):
+    """`L` (a loaded library handle) with the predictive-check entry points bound; resolved once per handle."""
+    return _bind(L, PPC_SYMBOLS, "_ppc")
+
+
+def load_ppc():
+    """The library with the predictive-check entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_ppc(load())
 
 
 def bind_covariance(L):

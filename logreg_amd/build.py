@@ -83,7 +83,8 @@ def _sources():
                                                                         os.path.join(INCLUDE, "logreg_hip_dense.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_pg.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_bridge.h"),
-                                                                        os.path.join(INCLUDE, "logreg_hip_rank.h")]
+                                                                        os.path.join(INCLUDE, "logreg_hip_rank.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_ppc.h")]
 
 
 def _dirs(alt: bool):

@@ -25,6 +25,7 @@
 #include "../../include/logreg_hip_pg.h"
 #include "../../include/logreg_hip_bridge.h"
 #include "../../include/logreg_hip_rank.h"
+#include "../../include/logreg_hip_ppc.h"
 
 #include <hip/hip_runtime.h>
 #define LR_STAMPS_HOST  // this unit also gets the host side of the development instrumentation (lr_stamps.h: empty in production builds)
@@ -54,6 +55,7 @@
 #include "lr_hessian.h"
 #include "lr_mfma.h"
 #include "lr_predict.h"
+#include "lr_ppc.h"
 #include "lr_loo.h"
 #include "lr_bridge.h"
 #include "lr_rank.h"
@@ -966,6 +968,241 @@ void lr_predict_destroy(lr_predict* pp) {
     if (pp->own_rows && pp->d_rows) (void)hipFree(pp->d_rows);
     free_all({pp->d_sign, pp->d_acc, pp->part.p, pp->in.p, pp->padded.p});
     delete pp;
+}
+
+// ---- posterior predictive checks from replicated outcomes (include/logreg_hip_ppc.h; kernels: lr_ppc.h) --------------------------------
+}  // extern "C"
+struct lr_ppc : Staged {
+    lr_model* m = nullptr;
+    int device = 0;
+    int64_t r = 0;
+    int G = 1;
+    bool labels = false;
+    uint64_t seed = 0;
+    void* d_rows = nullptr;          // [r][P] signed rows (the model's own d_rows when own_rows is false)
+    bool own_rows = false;
+    signed char* d_sign = nullptr;   // [r] 2 y - 1 (labels only)
+    unsigned char* d_grp = nullptr;  // [r] group labels (G > 1 only)
+    int64_t* d_off = nullptr;        // [G] where group g's run of hist starts
+    unsigned long long* d_tab = nullptr;  // hist [r + G] | row_ones [r] | counts [2]
+    double* d_mom = nullptr;         // [lr::kPpcState] the running moments
+    std::vector<int64_t> n_g, t_obs;
+    int64_t n = 0;                   // draws handed over = the index s of the next one
+    Workspace part, flags, dev;      // per-tile partials, finite flags and (D_obs, D_rep) of one sub-batch
+    size_t tab_cells() const { return (size_t)r + (size_t)G + (size_t)r + 2; }
+    unsigned long long* row_ones() const { return d_tab + r + G; }
+    unsigned long long* counts() const { return d_tab + 2 * r + G; }
+};
+namespace {
+static_assert(LR_PPC_MAX_GROUPS == lr::kPpcMaxGroups && LR_PPC_TAG == lr::TAG_PPC && LR_PPC_MOMENTS == lr::kPpcState - 1, "logreg_hip_ppc.h and lr_ppc.h");
+static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the integer tables are 64-bit words");
+
+constexpr size_t kPpcPartBytes = size_t(64) << 20;  // the most the per-tile partials of one sub-batch take (where four draws fit in it)
+constexpr int64_t kPpcMostSub = int64_t(1) << 20;
+int64_t ppc_tiles(int64_t r) { return (r + lr::kPpcBlock - 1) / lr::kPpcBlock; }
+size_t ppc_part_per_draw(int64_t r, int G) { return (size_t)ppc_tiles(r) * (2 * sizeof(double) + (size_t)G * sizeof(uint32_t)); }
+// The draws of one sub-batch: a function of (r, G) alone, a multiple of 4, at least 4.
+int64_t ppc_sub_batch(int64_t r, int G) {
+    const int64_t fit = (int64_t)(kPpcPartBytes / ppc_part_per_draw(r, G)) & ~int64_t(3);
+    return std::min(kPpcMostSub, std::max<int64_t>(4, fit));
+}
+// the workspaces for pieces of at most S0 draws
+int ppc_reserve(lr_ppc* pc, int64_t S0, bool terms) {
+    const size_t nb = (size_t)std::min(S0, ppc_sub_batch(pc->r, pc->G));
+    if (const int rc = pc->part.grow(nb * ppc_part_per_draw(pc->r, pc->G), "lr_ppc", "tile partials")) return rc;
+    if (const int rc = pc->flags.grow(nb * sizeof(uint32_t), "lr_ppc", "finite flags")) return rc;
+    return terms ? LR_OK : pc->dev.grow(nb * 2 * sizeof(double), "lr_ppc", "deviances");
+}
+
+struct PpcTerms {  // device outputs of lr_ppc_terms, and how many draws they hold already
+    int32_t* counts;
+    double* dev;
+    uint32_t* yrep;
+    int64_t words, done;
+};
+
+// S device-resident draws [S][P] whose first has the global index s0: sub-batch by sub-batch.  Every sub-batch but the last ends at a
+// multiple of 4 of the global index, so a Philox block is never computed in two of them.
+template <typename T, int P>
+int ppc_launch(lr_ppc* pc, const void* d_draws, int64_t S, int64_t s0, PpcTerms* to, hipStream_t st) {
+    const int64_t tiles = ppc_tiles(pc->r), sub = ppc_sub_batch(pc->r, pc->G), end = s0 + S;
+    const int64_t want_blocks = (int64_t)(pc->m->cus > 0 ? pc->m->cus : 256) * 4;
+    for (int64_t b = s0; b < end;) {
+        const int64_t e = std::min(end, (b + sub) & ~int64_t(3)), nb = e - b;
+        const T* d = static_cast<const T*>(d_draws) + (size_t)(b - s0) * P;
+        uint32_t* flags = static_cast<uint32_t*>(pc->flags.p);
+        double* part_d = static_cast<double*>(pc->part.p);
+        uint32_t* part_c = reinterpret_cast<uint32_t*>(part_d + (size_t)tiles * nb * 2);
+        hipLaunchKernelGGL(lr::k_ppc_flag<T>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d, nb, P, flags);
+        LR_HIP(hipGetLastError());
+        const int64_t span = e - (b & ~int64_t(3));
+        int64_t sl = std::max<int64_t>(1, std::min((want_blocks + tiles - 1) / tiles, (span + 63) / 64));
+        const int64_t per = ((span + sl - 1) / sl + 3) & ~int64_t(3);
+        sl = (span + per - 1) / per;  // every slice non-empty
+        const dim3 grid((unsigned)tiles, (unsigned)sl);
+        unsigned long long* ones = to ? nullptr : pc->row_ones();
+        uint32_t* yrep = to && to->yrep ? to->yrep + (size_t)to->done * to->words : nullptr;
+        const int64_t words = to ? to->words : 0;
+        if (pc->labels)
+            hipLaunchKernelGGL((lr::k_ppc_partial<T, P, true>), grid, dim3(lr::kPpcBlock), 0, st, static_cast<const T*>(pc->d_rows), pc->d_sign, pc->d_grp, pc->r, pc->G, d,
+                               flags, b, e, per, (uint32_t)pc->seed, (uint32_t)(pc->seed >> 32), part_d, part_c, ones, yrep, words);
+        else
+            hipLaunchKernelGGL((lr::k_ppc_partial<T, P, false>), grid, dim3(lr::kPpcBlock), 0, st, static_cast<const T*>(pc->d_rows), pc->d_sign, pc->d_grp, pc->r, pc->G, d,
+                               flags, b, e, per, (uint32_t)pc->seed, (uint32_t)(pc->seed >> 32), part_d, part_c, ones, yrep, words);
+        LR_HIP(hipGetLastError());
+        double* dev = to ? to->dev + (size_t)to->done * 2 : static_cast<double*>(pc->dev.p);
+        hipLaunchKernelGGL(lr::k_ppc_fold, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, part_d, part_c, flags, nb, tiles, pc->G, pc->labels ? 1 : 0, pc->d_off,
+                           pc->d_tab, pc->counts(), dev, to ? to->counts + (size_t)to->done * pc->G : nullptr);
+        LR_HIP(hipGetLastError());
+        if (to) {
+            to->done += nb;
+        } else {
+            hipLaunchKernelGGL(lr::k_ppc_moments, dim3(1), dim3(lr::kPpcMomBlock), 0, st, dev, flags, nb, pc->d_mom);
+            LR_HIP(hipGetLastError());
+            pc->n += nb;
+        }
+        b = e;
+    }
+    return LR_OK;
+}
+int ppc_launch_any(lr_ppc* pc, const void* d_draws, int64_t S, int64_t s0, PpcTerms* to, hipStream_t st) {
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_ALL, pc->m->dtype, pc->m->P, ppc_launch, pc, d_draws, S, s0, to, st)
+    return fail(LR_ERR_UNSUPPORTED, "lr_ppc: unsupported padded width %d", pc->m->P);
+}
+}  // namespace
+extern "C" {
+
+int lr_ppc_create(lr_model* m, const double* X_new, const double* y_new, int64_t r, const int32_t* groups, int32_t G, uint64_t seed, lr_ppc** out) {
+    if (!m || !out) return fail(LR_ERR_INVALID, "lr_ppc_create: model / out is NULL");
+    if (r <= 0) return fail(LR_ERR_INVALID, "lr_ppc_create: r must be positive (got %lld)", (long long)r);
+    if (r > 0x7FFFFFFFll) return fail(LR_ERR_UNSUPPORTED, "lr_ppc_create: r = %lld is beyond the 32-bit row word of the random stream", (long long)r);
+    if (G < 1 || G > LR_PPC_MAX_GROUPS) return fail(LR_ERR_INVALID, "lr_ppc_create: G must be 1 .. %d (got %d)", LR_PPC_MAX_GROUPS, G);
+    if (!groups && G != 1) return fail(LR_ERR_INVALID, "lr_ppc_create: groups = NULL means one group, G = %d", G);
+    if (!X_new && y_new) return fail(LR_ERR_INVALID, "lr_ppc_create: y_new without X_new (X_new = NULL means the model's own design AND labels)");
+    if (!X_new && r != m->n) return fail(LR_ERR_INVALID, "lr_ppc_create: X_new = NULL means the model's own %lld rows, r = %lld", (long long)m->n, (long long)r);
+    if (y_new)
+        for (int64_t i = 0; i < r; ++i)
+            if (y_new[i] != 0.0 && y_new[i] != 1.0) return fail(LR_ERR_INVALID, "lr_ppc_create: y_new[%lld]=%g is not 0/1", (long long)i, y_new[i]);
+    if (groups)
+        for (int64_t i = 0; i < r; ++i)
+            if (groups[i] < 0 || groups[i] >= G) return fail(LR_ERR_INVALID, "lr_ppc_create: groups[%lld]=%d is outside [0, %d)", (long long)i, groups[i], G);
+    std::vector<unsigned char> host;
+    std::vector<signed char> sg;
+    if (X_new) {  // (non-finite X_new is refused here, ahead of any device access)
+        if (y_new) sg.resize((size_t)r);
+        if (const int rc = signed_rows("lr_ppc_create: X_new", X_new, y_new, r, m->p, m->P, m->dtype, &host, y_new ? sg.data() : nullptr)) return rc;
+    }
+    LR_HIP(hipSetDevice(m->device));
+    lr_ppc* pc = new lr_ppc();
+    pc->m = m;
+    pc->device = m->device;
+    pc->r = r;
+    pc->G = G;
+    pc->seed = seed;
+    pc->labels = !X_new || y_new;
+    const std::vector<signed char>& signs = X_new ? sg : m->ysign;
+    pc->n_g.assign((size_t)G, 0);
+    pc->t_obs.assign((size_t)G, pc->labels ? 0 : -1);
+    std::vector<unsigned char> grp(groups && G > 1 ? (size_t)r : 0);
+    for (int64_t i = 0; i < r; ++i) {
+        const int g = groups ? groups[i] : 0;
+        if (!grp.empty()) grp[(size_t)i] = (unsigned char)g;
+        pc->n_g[(size_t)g] += 1;
+        if (pc->labels && signs[(size_t)i] > 0) pc->t_obs[(size_t)g] += 1;
+    }
+    std::vector<int64_t> off((size_t)G, 0);
+    for (int g = 1; g < G; ++g) off[(size_t)g] = off[(size_t)g - 1] + pc->n_g[(size_t)g - 1] + 1;
+    int rc = LR_OK;
+    if (X_new) {
+        pc->own_rows = true;
+        rc = upload("lr_ppc_create", "rows", host.data(), host.size(), &pc->d_rows, LR_ERR_HIP);
+    } else {
+        pc->d_rows = m->d_rows;
+    }
+    if (!rc && pc->labels) rc = upload("lr_ppc_create", "labels", signs.data(), (size_t)r, (void**)&pc->d_sign, LR_ERR_HIP);
+    if (!rc && !grp.empty()) rc = upload("lr_ppc_create", "group labels", grp.data(), grp.size(), (void**)&pc->d_grp, LR_ERR_HIP);
+    if (!rc) rc = upload("lr_ppc_create", "group offsets", off.data(), off.size() * sizeof(int64_t), (void**)&pc->d_off, LR_ERR_HIP);
+    if (!rc && hipMalloc((void**)&pc->d_tab, pc->tab_cells() * sizeof(uint64_t)) != hipSuccess) rc = fail(LR_ERR_NOMEM, "lr_ppc_create: allocating the tables failed");
+    if (!rc && hipMalloc((void**)&pc->d_mom, lr::kPpcState * sizeof(double)) != hipSuccess) rc = fail(LR_ERR_NOMEM, "lr_ppc_create: allocating the moments failed");
+    if (!rc) rc = lr_ppc_reset(pc);
+    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(LR_ERR_HIP, "lr_ppc_create: clearing the tables failed");
+    if (rc) {
+        lr_ppc_destroy(pc);
+        return rc;
+    }
+    *out = pc;
+    return LR_OK;
+}
+
+int lr_ppc_accumulate(lr_ppc* pc, const void* draws, int64_t S, int32_t on_device, void* stream) {
+    if (!pc || !draws) return fail(LR_ERR_INVALID, "lr_ppc_accumulate: accumulator / draws is NULL");
+    if (S <= 0) return fail(LR_ERR_INVALID, "lr_ppc_accumulate: S must be positive (got %lld)", (long long)S);
+    LR_HIP(hipSetDevice(pc->device));
+    return stage_draws(
+        "lr_ppc", *pc, pc->m, Feed{draws, S, on_device != 0, (hipStream_t)stream}, [pc](int64_t S0) { return ppc_reserve(pc, S0, false); },
+        [pc](const void* d_draws, int64_t Sb, hipStream_t st) { return ppc_launch_any(pc, d_draws, Sb, pc->n, nullptr, st); });
+}
+
+int lr_ppc_terms(lr_ppc* pc, const void* draws, int64_t S, int64_t first_index, int32_t on_device, void* stream, int32_t* counts_out, double* dev_out,
+                 uint32_t* yrep_out) {
+    if (!pc || !draws || !counts_out || !dev_out) return fail(LR_ERR_INVALID, "lr_ppc_terms: accumulator / draws / counts_out / dev_out is NULL");
+    if (S <= 0) return fail(LR_ERR_INVALID, "lr_ppc_terms: S must be positive (got %lld)", (long long)S);
+    if (first_index < 0) return fail(LR_ERR_INVALID, "lr_ppc_terms: first_index must be >= 0 (got %lld)", (long long)first_index);
+    LR_HIP(hipSetDevice(pc->device));
+    const int64_t words = (pc->r + 31) / 32;
+    const size_t b_dev = (size_t)S * 2 * sizeof(double), b_cnt = (size_t)S * pc->G * sizeof(int32_t), b_rep = yrep_out ? (size_t)S * words * sizeof(uint32_t) : 0;
+    DevBuf buf;
+    if (buf.alloc(b_dev + b_cnt + b_rep) != 0) return fail(LR_ERR_NOMEM, "lr_ppc_terms: allocating %zu bytes of output failed", b_dev + b_cnt + b_rep);
+    unsigned char* base = static_cast<unsigned char*>(buf.p);
+    PpcTerms to{reinterpret_cast<int32_t*>(base + b_dev), reinterpret_cast<double*>(base), yrep_out ? reinterpret_cast<uint32_t*>(base + b_dev + b_cnt) : nullptr, words, 0};
+    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = stage_draws(
+            "lr_ppc", *pc, pc->m, Feed{draws, S, on_device != 0, st}, [pc](int64_t S0) { return ppc_reserve(pc, S0, true); },
+            [pc, first_index, &to](const void* d_draws, int64_t Sb, hipStream_t s) { return ppc_launch_any(pc, d_draws, Sb, first_index + to.done, &to, s); })) {
+        (void)hipStreamSynchronize(st);  // the output buffer is about to be freed
+        return rc;
+    }
+    LR_HIP(hipMemcpyAsync(dev_out, to.dev, b_dev, hipMemcpyDeviceToHost, st));
+    LR_HIP(hipMemcpyAsync(counts_out, to.counts, b_cnt, hipMemcpyDeviceToHost, st));
+    if (yrep_out) LR_HIP(hipMemcpyAsync(yrep_out, to.yrep, b_rep, hipMemcpyDeviceToHost, st));
+    LR_HIP(hipStreamSynchronize(st));
+    return LR_OK;
+}
+
+int lr_ppc_result(lr_ppc* pc, uint64_t* hist, uint64_t* row_ones, uint64_t* counts, double* moments, int64_t* t_obs, int64_t* n_g, int64_t* n_draws) {
+    if (!pc) return fail(LR_ERR_INVALID, "lr_ppc_result: accumulator is NULL");
+    LR_HIP(hipSetDevice(pc->device));
+    double state[lr::kPpcState];
+    if (hist) LR_HIP(hipMemcpyAsync(hist, pc->d_tab, ((size_t)pc->r + pc->G) * sizeof(uint64_t), hipMemcpyDeviceToHost, pc->last));
+    if (row_ones) LR_HIP(hipMemcpyAsync(row_ones, pc->row_ones(), (size_t)pc->r * sizeof(uint64_t), hipMemcpyDeviceToHost, pc->last));
+    if (counts) LR_HIP(hipMemcpyAsync(counts, pc->counts(), 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, pc->last));
+    LR_HIP(hipMemcpyAsync(state, pc->d_mom, sizeof(state), hipMemcpyDeviceToHost, pc->last));
+    LR_HIP(hipStreamSynchronize(pc->last));
+    if (moments) {
+        for (int k = 0; k < LR_PPC_MOMENTS; ++k) moments[k] = state[0] > 0.0 ? state[k + 1] : (double)NAN;
+        if (!pc->labels) moments[0] = moments[1] = (double)NAN;
+    }
+    if (t_obs) std::copy(pc->t_obs.begin(), pc->t_obs.end(), t_obs);
+    if (n_g) std::copy(pc->n_g.begin(), pc->n_g.end(), n_g);
+    if (n_draws) *n_draws = pc->n;
+    return LR_OK;
+}
+
+int lr_ppc_reset(lr_ppc* pc) {
+    if (!pc) return fail(LR_ERR_INVALID, "lr_ppc_reset: accumulator is NULL");
+    LR_HIP(hipSetDevice(pc->device));
+    LR_HIP(hipMemsetAsync(pc->d_tab, 0, pc->tab_cells() * sizeof(uint64_t), pc->last));
+    LR_HIP(hipMemsetAsync(pc->d_mom, 0, lr::kPpcState * sizeof(double), pc->last));
+    pc->n = 0;
+    return LR_OK;
+}
+
+void lr_ppc_destroy(lr_ppc* pc) {
+    if (!pc) return;
+    (void)hipSetDevice(pc->device);
+    if (pc->own_rows && pc->d_rows) (void)hipFree(pc->d_rows);
+    free_all({pc->d_sign, pc->d_grp, pc->d_off, pc->d_tab, pc->d_mom, pc->part.p, pc->flags.p, pc->dev.p, pc->in.p, pc->padded.p});
+    delete pc;
 }
 
 // ---- autocorrelation and Geyer ESS of the kept draws (include/logreg_hip_acf.h; kernels: lr_acf.h) ------------------------------------

@@ -32,6 +32,7 @@ namespace lr {
 // NUTS (lr_nuts.h) adds block 0x40000000 | d (doubling d < 16: direction bit, merge uniform) and 0x20000000 | k/4 (leaf uniforms,
 // k < 1023): disjoint from the normal blocks and from TAG_UNIFORM.
 // Polya-Gamma (lr_pg.h) uses 0x10000000 | b << 16 | row; bridge sampling (lr_bridge.h) 0x08000000 | b, b < 32, with counter (j lo, j hi, 0, .).
+// The posterior predictive check (lr_ppc.h) uses 0x04000000 with key = its own seed and counter (q lo, q hi, row, .), q = draw index / 4.
 // 24-bit uniforms u = ((w >> 8) + 0.5) * 2^-24 are exact in fp32 and fp64.
 // ------------------------------------------------------------------------------------------
 struct U4 { uint32_t x, y, z, w; };

@@ -711,13 +711,16 @@ def _accumulator_class(keyword):
     if keyword == "bridge":
         from .bridge import Bridge
         return Bridge, "a Bridge"
+    if keyword == "check":
+        from .ppc import PredictiveCheck
+        return PredictiveCheck, "a PredictiveCheck"
     from .loo import PsisLoo
     return PsisLoo, "a PsisLoo"
 
 
 def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None, chain_offset=0, ll=None,
          group=0, mode="auto", return_info=False, summary_only=False, max_batches=16, precision="auto", plan_chains=0, plan_first=0,
-         autocorr=None, rank=None, loo=None, bridge=None, covariance=None, marginals=None, predictive=None):
+         autocorr=None, rank=None, check=None, loo=None, bridge=None, covariance=None, marginals=None, predictive=None):
     """Run a chain (or C chains): `mat[i]` = state after (i+1)*thin iterations (fit-np-hmc.py:89-103).
 
     Fused kernels run on the device; `init` of shape [p] returns a float64 `[iters, p]` matrix
@@ -771,6 +774,11 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     `return_info=True`, the info dict -- gains `"bridge": bridge.result()` (logml, its standard error with n_eff = the number of draws;
     `bridge.result(n_eff=...)` afterwards takes the effective size from `autocorr`).  Chains, states, statistics and accept counts are
     those of the same call without it.
+    `check` (fused kernels): a `PredictiveCheck` of the kernel's own model.  Every chunk's block of kept samples is replicated on the
+    device where `predictive` is fed (draw index = the draws it already holds, time-major); the summary dict -- or, with
+    `return_info=True`, the info dict -- gains `"check": check.result()` (per group the observed and replicated counts with their tail
+    probabilities, the deviance check, the per-row frequency of ones).  Chains, states, statistics and accept counts are those of the same
+    call without it.
     A `pgKernel` (the Polya-Gamma Gibbs sampler) has no accept count: `return_info=True` and `summary_only=True` report its per-chain
     counters instead (`proposals`, `series_terms`, `skipped` and the two ratios of `ChainSet.pg_info`); `accept_rate` is the share of
     sweeps that were not skipped.
@@ -779,9 +787,9 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     """
     # the accumulators given: refused in the order of the keywords here, fed and reported in the order of `accs`
     given = {name: acc for name, acc in (("predictive", predictive), ("autocorr", autocorr), ("rank", rank), ("marginals", marginals), ("covariance", covariance), ("loo", loo),
-                                              ("bridge", bridge))
+                                              ("bridge", bridge), ("check", check))
              if acc is not None}
-    accs = [(name, given[name]) for name in ("autocorr", "rank", "marginals", "covariance", "loo", "bridge", "predictive") if name in given]
+    accs = [(name, given[name]) for name in ("autocorr", "rank", "marginals", "covariance", "loo", "bridge", "check", "predictive") if name in given]
     if not isinstance(kernel, FusedKernel):
         for name in given:
             raise ValueError(f"{name}= needs a fused kernel (the closures of a LogReg)")
