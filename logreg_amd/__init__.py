@@ -18,7 +18,7 @@ from .marginals import Marginals, marginal_grid, merge_marginals  # noqa: F401
 from .covariance import Covariance, covariance_scaling, merge_covariance  # noqa: F401
 from .data import load_pima, load_pima_parquet, synthetic_logreg  # noqa: F401
 from .diagnostics import describe, ess_geyer, ess_per_param, ess_pooled, split_rhat, summarise  # noqa: F401
-from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKernel, nutsKernel, pgKernel, rwProposal,  # noqa: F401
+from .kernels import (ChainSet, FusedKernel, hmcKernel, malaKernel, mcmc, mhKernel, nutsKernel, pgKernel, hsKernel, rwProposal,  # noqa: F401
                       ulKernel)
 from .adapt import nuts_warmup, nuts_warmup_dense, nuts_warmup_stepwise  # noqa: F401
 from .model import DeviceArray, LogReg  # noqa: F401
@@ -30,7 +30,7 @@ from .ppc import PredictiveCheck, ppc_from_table  # noqa: F401
 from .bridge import Bridge, bridge_compare, bridge_from_table, bridge_from_terms, bridge_proposal, bridge_sampling  # noqa: F401
 from .output import print_summary, read_parquet, to_frame, write_parquet  # noqa: F401
 
-__all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "malaKernel", "hmcKernel", "ulKernel", "nutsKernel", "pgKernel",
+__all__ = ["LogReg", "DeviceArray", "ChainSet", "FusedKernel", "mhKernel", "malaKernel", "hmcKernel", "ulKernel", "nutsKernel", "pgKernel", "hsKernel",
            "rwProposal", "mcmc", "load_pima", "load_pima_parquet", "synthetic_logreg", "summarise", "describe",
            "ess_geyer", "ess_per_param", "ess_pooled", "split_rhat", "device_count", "LogregHipError", "find_map", "laplace_metric", "overdispersed_init", "write_parquet",
            "read_parquet", "to_frame", "print_summary", "PosteriorPredictive", "merge_predictive", "predict_proba", "waic", "waic_from_table", "Autocorr", "merge_autocorr", "Marginals", "marginal_grid", "merge_marginals", "Covariance", "covariance_scaling", "merge_covariance",

@@ -213,6 +213,23 @@ PG_SYMBOLS = {
     "lr_pg_omega": (C.c_int, [_vp, _vp, _op, _vp]),
 }
 
+class HsPrior(C.Structure):  # lr_hs_prior (include/logreg_hip_hs.h)
+    _fields_ = [("shrink", C.c_void_p), ("global_scale", C.c_double)]
+
+
+class HsCounters(C.Structure):  # lr_hs_counters
+    _fields_ = [("proposals", C.c_uint64), ("series_terms", C.c_uint64), ("skipped", C.c_uint32), ("clamped", C.c_uint32)]
+
+
+HS_TAG = 0x02000000  # LR_HS_TAG
+HS_MIN, HS_MAX = 1e-100, 1e100  # LR_HS_MIN, LR_HS_MAX
+# name -> (restype, argtypes); every symbol include/logreg_hip_hs.h declares.  A table of its own like PG_SYMBOLS, bound on first use
+# (load_hs)
+HS_SYMBOLS = {
+    "lr_run_hs": (C.c_int, [_vp, C.POINTER(HsPrior), _vp, _vp, _op, _vp, _vp, _vp]),
+    "lr_hs_hyper": (C.c_int, [_vp, C.POINTER(HsPrior), _vp, _vp, _op, _vp, _vp]),
+}
+
 BRIDGE_ROWS = 12  # LR_BRIDGE_ROWS: logml, se, iterations, converged, N1, N2, n_eff used, non-finite terms, min / max of l1 and of l2
 BRIDGE_MAX_DRAWS = 1 << 20  # LR_BRIDGE_MAX_DRAWS
 BRIDGE_TAG = 0x08000000  # LR_BRIDGE_TAG
@@ -260,6 +277,7 @@ PPC_SYMBOLS = {
 _lib = None
 _nuts = None
 _pg = None
+_hs = None
 _dense = None
 _factor = None
 _predict = None
@@ -416,6 +434,16 @@ def bind_pg(L):
 def load_pg():
     """The library with the Polya-Gamma entry points bound (the same liblogreg_hip.so as load())."""
     return bind_pg(load())
+
+
+def bind_hs(L):
+    """`L` (a loaded library handle) with the horseshoe Polya-Gamma entry points bound; resolved once per handle."""
+    return _bind(L, HS_SYMBOLS, "_hs")
+
+
+def load_hs():
+    """The library with the horseshoe Polya-Gamma entry points bound (the same liblogreg_hip.so as load())."""
+    return bind_hs(load())
 
 
 def load():

@@ -82,6 +82,7 @@ def _sources():
                                                                         os.path.join(INCLUDE, "logreg_hip_adapt_tall.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_dense.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_pg.h"),
+                                                                        os.path.join(INCLUDE, "logreg_hip_hs.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_bridge.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_rank.h"),
                                                                         os.path.join(INCLUDE, "logreg_hip_ppc.h")]

@@ -23,6 +23,7 @@
 #include "../../include/logreg_hip_adapt_tall.h"
 #include "../../include/logreg_hip_dense.h"
 #include "../../include/logreg_hip_pg.h"
+#include "../../include/logreg_hip_hs.h"
 #include "../../include/logreg_hip_bridge.h"
 #include "../../include/logreg_hip_rank.h"
 #include "../../include/logreg_hip_ppc.h"
@@ -49,6 +50,7 @@
 #include "lr_nuts.h"
 #include "lr_nuts_dense.h"
 #include "lr_pg.h"
+#include "lr_hs.h"
 #include "lr_dense.h"
 #include "lr_adapt.h"
 #include "lr_dense_adapt.h"
@@ -136,7 +138,8 @@ int staged(const HostBuf (&b)[N], Launch&& launch) {
 }
 
 // The arrays of a run.  tally: accept counts (uint32 per chain), NUTS counters or Polya-Gamma counters, tally_item bytes per chain; launches add to it, so it
-// is copied in as well as out.  lp_state: RWMH / MALA only.  depth_out: NUTS only.
+// is copied in as well as out.  lp_state: RWMH / MALA only.  depth_out: NUTS only.  aux (in/out, aux_item bytes per chain) and aux_out
+// (aux_out_item bytes per chain and kept row): the horseshoe's hyper-state and its scale_out.
 struct RunArrays {
     void* state;
     double* lp_state;
@@ -144,6 +147,10 @@ struct RunArrays {
     void* tally;
     size_t tally_item;
     int8_t* depth_out;
+    void* aux = nullptr;
+    size_t aux_item = 0;
+    void* aux_out = nullptr;
+    size_t aux_out_item = 0;
 };
 
 // The front every lr_run_* shares, after the checks of its own parameters: check the options and arrays, plan, then either enqueue on
@@ -164,11 +171,12 @@ int run_request(lr_model* m, int kind, int max_depth, const lr_run_opts* o, cons
     const size_t C = (size_t)o->n_chains, sbytes = C * m->p * m->esize();
     const HostBuf b[] = {{a.state, sbytes, true, true}, {a.lp_state, C * sizeof(double), true, true}, {a.out, (size_t)o->iters * sbytes, false, true},
                          {a.tally, C * a.tally_item, true, true}, {a.depth_out, (size_t)o->iters * C, false, true},
-                         {o->stats, (size_t)o->stats_slots * C * 2 * m->p * sizeof(double), true, true}};
+                         {o->stats, (size_t)o->stats_slots * C * 2 * m->p * sizeof(double), true, true},
+                         {a.aux, C * a.aux_item, true, true}, {a.aux_out, (size_t)o->iters * C * a.aux_out_item, false, true}};
     return staged(b, [&](void* const* d) {
         lr_run_opts od = *o;
         od.stats = static_cast<double*>(d[5]);
-        return launch(pl, nullptr, &od, RunArrays{d[0], static_cast<double*>(d[1]), d[2], d[3], a.tally_item, static_cast<int8_t*>(d[4])});
+        return launch(pl, nullptr, &od, RunArrays{d[0], static_cast<double*>(d[1]), d[2], d[3], a.tally_item, static_cast<int8_t*>(d[4]), d[6], a.aux_item, d[7], a.aux_out_item});
     });
 }
 
@@ -328,9 +336,9 @@ int run_nuts(lr_model* m, int kind, double eps, int max_depth, const lr_run_opts
 // ---- Polya-Gamma Gibbs (include/logreg_hip_pg.h; kernel: lr_pg.h).  omega_out: lr_pg_omega (the draws of one sweep, nothing else written)
 static_assert(sizeof(lr::PgCounters) == sizeof(lr_pg_counters) && LR_KIND_PG == lr::kKindPg && LR_PG_TAG == lr::TAG_PG &&
               LR_PG_MAX_ROUNDS == lr::kPgMaxRounds && LR_PG_MAX_TRIALS == lr::kPgMaxTrials && LR_PG_MAX_TERMS == lr::kPgMaxTerms, "logreg_hip_pg.h and lr_pg.h");
+// the PgArgs of a launch, from the model, the options and the arrays
 template <typename T, int P>
-int pg_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
-    auto ma = model_args<T, P>(m);
+lr::PgArgs<T, P> pg_args(const lr_model* m, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
     lr::PgArgs<T, P> pa{};
     pa.state = static_cast<T*>(d.state);
     pa.out = static_cast<T*>(d.out);
@@ -348,6 +356,12 @@ int pg_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o,
         pa.ivar[j] = j < m->p ? m->inv_var[j] : 1.0;
     }
     pa.stats = lr::StatsArgs{o->stats, o->stats_batch, o->stats_first};
+    return pa;
+}
+template <typename T, int P>
+int pg_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
+    auto ma = model_args<T, P>(m);
+    const lr::PgArgs<T, P> pa = pg_args<T, P>(m, o, d, omega_out);
     const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_PG, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
     const int rc = m->table->launch_pg(&cfg, o->n_chains, &ma, &pa);
     if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "PG launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
@@ -356,6 +370,62 @@ int pg_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o,
 int pg_launch_any(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, void* omega_out) {
     LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, pg_launch, m, pl, st, o, d, omega_out)
     return bad_width(m);
+}
+
+// ---- horseshoe Polya-Gamma Gibbs (include/logreg_hip_hs.h; kernel: lr_hs.h).  The prior as the kernel takes it; hyper_in != null:
+// lr_hs_hyper (steps 5-7 of one iteration from hyper_in into d.aux, nothing else written)
+static_assert(sizeof(lr_hs_counters) == sizeof(lr::PgCounters) && offsetof(lr_hs_counters, clamped) == offsetof(lr::PgCounters, reserved) &&
+              LR_HS_TAG == lr::TAG_HS && LR_HS_BLOCK_GLOBAL == lr::kHsBlockGlobal && LR_HS_BLOCK_GAMMA == lr::kHsBlockGamma && LR_HS_MIN == lr::kHsLo &&
+              LR_HS_MAX == lr::kHsHi, "logreg_hip_hs.h and lr_hs.h");
+struct HsPrior {
+    uint32_t shrink;
+    int m;
+    double inv_tau0sq;
+};
+template <typename T, int P>
+int hs_launch(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, const HsPrior& pr, const double* hyper_in) {
+    auto ma = model_args<T, P>(m);
+    lr::HsArgs<T, P> ha{};
+    ha.pg = pg_args<T, P>(m, o, d, nullptr);
+    ha.hyper_in = hyper_in ? hyper_in : static_cast<const double*>(d.aux);
+    ha.hyper_out = static_cast<double*>(d.aux);
+    ha.scale_out = static_cast<double*>(d.aux_out);
+    ha.inv_tau0sq = pr.inv_tau0sq;
+    ha.shrink = pr.shrink;
+    ha.nexp = (pr.m + 1) / 2;
+    ha.odd = (pr.m + 1) & 1;
+    ha.hyper_only = hyper_in ? 1 : 0;
+    const lr::LaunchCfg cfg{pl.mode, pl.G, pl.R, LR_KIND_PG, st, pl.lds_bytes, m->dbg.residency_cap ? m->cus : 0};
+    const int rc = m->table->launch_hs(&cfg, o->n_chains, &ma, &ha);
+    if (rc != 0) return fail(rc == -3 ? LR_ERR_UNSUPPORTED : LR_ERR_HIP, "horseshoe PG launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return LR_OK;
+}
+int hs_launch_any(lr_model* m, const Plan& pl, hipStream_t st, const lr_run_opts* o, const RunArrays& d, const HsPrior& pr, const double* hyper_in) {
+    if (!m->table->launch_hs) return fail(LR_ERR_UNSUPPORTED, "horseshoe PG: no kernel for padded p = %d", m->P);
+    LR_RETURN_BY_DTYPE_WIDTH(LR_WIDTHS_FUSED, m->dtype, m->P, hs_launch, m, pl, st, o, d, pr, hyper_in)
+    return bad_width(m);
+}
+// what lr_run_hs and lr_hs_hyper refuse about the prior and a hyper-state in host memory, ahead of any device access
+int hs_check(const char* who, const lr_model* m, const lr_hs_prior* prior, const lr_run_opts* o, const double* hyper, const char* hyper_name, HsPrior* pr) {
+    if (!m) return fail(LR_ERR_INVALID, "model is NULL");
+    if (!prior) return fail(LR_ERR_INVALID, "%s: prior is NULL", who);
+    if (!prior->shrink) return fail(LR_ERR_INVALID, "%s: prior->shrink is NULL", who);
+    if (!(prior->global_scale > 0) || !std::isfinite(prior->global_scale)) return fail(LR_ERR_INVALID, "%s: global_scale must be finite and > 0", who);
+    if (m->p > 32) return fail(LR_ERR_UNSUPPORTED, "PG: p = %d > 32 -- the Polya-Gamma kernel keeps a chain's p x p matrix on 16 lanes, up to p = 32", m->p);
+    *pr = HsPrior{0u, 0, 1.0 / (prior->global_scale * prior->global_scale)};
+    for (int j = 0; j < m->p; ++j)
+        if (prior->shrink[j]) {
+            pr->shrink |= 1u << j;
+            ++pr->m;
+        }
+    if (!hyper) return fail(LR_ERR_INVALID, "%s is NULL", hyper_name);
+    if (o && !o->on_device && o->n_chains > 0) {
+        const size_t w = 2 * (size_t)m->p + 2;
+        for (size_t i = 0; i < (size_t)o->n_chains * w; ++i)
+            if (!(hyper[i] >= LR_HS_MIN && hyper[i] <= LR_HS_MAX))
+                return fail(LR_ERR_INVALID, "%s[%zu][%zu] = %g must be finite and > 0 (in [%g, %g])", hyper_name, i / w, i % w, hyper[i], LR_HS_MIN, LR_HS_MAX);
+    }
+    return LR_OK;
 }
 
 // signed rows  xs_i = s_i x_i  of a design X [n][p], zero-padded to P columns, in the compute dtype;  s_i = 2 y_i - 1, or 1 without labels
@@ -749,6 +819,41 @@ int lr_pg_omega(lr_model* m, const void* state, const lr_run_opts* o, void* omeg
     const size_t C = (size_t)one.n_chains;
     const HostBuf b[] = {{const_cast<void*>(state), C * m->p * m->esize(), true, false}, {omega_out, C * (size_t)m->n * m->esize(), false, true}};
     return staged(b, [&](void* const* d) { return pg_launch_any(m, pl, nullptr, &one, RunArrays{d[0], nullptr, nullptr, nullptr, 0, nullptr}, d[1]); });
+}
+
+// horseshoe Polya-Gamma Gibbs (include/logreg_hip_hs.h): lr_run_pg's request with the hyper-state and scale_out as two more arrays
+int lr_run_hs(lr_model* m, const lr_hs_prior* prior, void* state, double* hyper, const lr_run_opts* o, void* out, double* scale_out, lr_hs_counters* counters) {
+    HsPrior pr;
+    if (const int rc = hs_check("lr_run_hs", m, prior, o, hyper, "hyper", &pr)) return rc;
+    const size_t p = (size_t)m->p;
+    return run_request(m, LR_KIND_PG, 0, o, RunArrays{state, nullptr, out, counters, sizeof(lr_hs_counters), nullptr, hyper, (2 * p + 2) * sizeof(double), scale_out, (p + 1) * sizeof(double)},
+                       [&](const Plan& pl, hipStream_t st, const lr_run_opts* oo, const RunArrays& d) { return hs_launch_any(m, pl, st, oo, d, pr, nullptr); });
+}
+
+// steps 5-7 of the iteration at opts->iter_offset: state and hyper_in are read, hyper_out (and `clamped`) written
+int lr_hs_hyper(lr_model* m, const lr_hs_prior* prior, const void* state, const double* hyper_in, const lr_run_opts* o, double* hyper_out, lr_hs_counters* counters) {
+    HsPrior pr;
+    if (const int rc0 = hs_check("lr_hs_hyper", m, prior, o, hyper_in, "hyper_in", &pr)) return rc0;
+    if (!o) return fail(LR_ERR_INVALID, "opts is NULL");
+    if (!hyper_out) return fail(LR_ERR_INVALID, "hyper_out is NULL");
+    lr_run_opts one = *o;  // (iters and thin are not read: one iteration)
+    one.iters = 1;
+    one.thin = 1;
+    one.stats = nullptr;
+    int rc = check_opts(m, &one, true);
+    if (rc) return rc;
+    if (!state) return fail(LR_ERR_INVALID, "state is NULL");
+    LR_HIP(hipSetDevice(m->device));
+    Plan pl;
+    if ((rc = plan_run(m, LR_KIND_PG, &one, 0, &pl))) return rc;
+    const size_t C = (size_t)one.n_chains, hbytes = C * (2 * (size_t)m->p + 2) * sizeof(double);
+    if (one.on_device)
+        return hs_launch_any(m, pl, (hipStream_t)one.stream, &one, RunArrays{const_cast<void*>(state), nullptr, nullptr, counters, sizeof(lr_hs_counters), nullptr, hyper_out}, pr, hyper_in);
+    const HostBuf b[] = {{const_cast<void*>(state), C * m->p * m->esize(), true, false}, {const_cast<double*>(hyper_in), hbytes, true, false}, {hyper_out, hbytes, false, true},
+                         {counters, C * sizeof(lr_hs_counters), true, true}};
+    return staged(b, [&](void* const* d) {
+        return hs_launch_any(m, pl, nullptr, &one, RunArrays{d[0], nullptr, nullptr, d[3], sizeof(lr_hs_counters), nullptr, d[2]}, pr, static_cast<const double*>(d[1]));
+    });
 }
 
 int lr_hessian(lr_model* m, const double* beta, double* lpost, double* grad, double* hess, void* stream) {

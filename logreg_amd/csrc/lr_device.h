@@ -33,6 +33,7 @@ namespace lr {
 // k < 1023): disjoint from the normal blocks and from TAG_UNIFORM.
 // Polya-Gamma (lr_pg.h) uses 0x10000000 | b << 16 | row; bridge sampling (lr_bridge.h) 0x08000000 | b, b < 32, with counter (j lo, j hi, 0, .).
 // The posterior predictive check (lr_ppc.h) uses 0x04000000 with key = its own seed and counter (q lo, q hi, row, .), q = draw index / 4.
+// The horseshoe's hyper-step (lr_hs.h) uses 0x02000000 | b, b < 41.
 // 24-bit uniforms u = ((w >> 8) + 0.5) * 2^-24 are exact in fp32 and fp64.
 // ------------------------------------------------------------------------------------------
 struct U4 { uint32_t x, y, z, w; };

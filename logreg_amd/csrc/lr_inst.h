@@ -86,6 +86,8 @@ struct InstTable {
     int (*launch_tall_nuts)(hipStream_t, const void* tall_args, const void* nuts_args, int phase, int64_t iter, int s, int d, int i, int64_t out_row, int flag);
     // ... k_tall_nuts_update_tuned (the warm-up): `nuts_args` is a NutsTallTunedArgs<T,P>, and `phase` may be NPH_CARRY
     int (*launch_tall_nuts_tuned)(hipStream_t, const void* tall_args, const void* nuts_args, int phase, int64_t iter, int s, int d, int i, int64_t out_row, int flag);
+    // the horseshoe Polya-Gamma Gibbs sampler (lr_hs.h): launch_pg's layout and LDS; `hs_args` is an HsArgs<T, P>; null where launch_pg is
+    int (*launch_hs)(const LaunchCfg*, int64_t C, const void* model_args, const void* hs_args);
 };
 
 }  // namespace lr

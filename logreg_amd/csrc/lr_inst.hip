@@ -5,6 +5,7 @@
 #include "lr_nuts.h"
 #include "lr_nuts_dense.h"
 #include "lr_pg.h"
+#include "lr_hs.h"
 #include "lr_tall.h"
 #include "lr_tall_nuts.h"
 #if LR_DTYPE == 0 && LR_P >= 8
@@ -309,8 +310,15 @@ int launch_pg(const LaunchCfg* cfg, int64_t C, const void* model_args, const voi
                                       *static_cast<const PgArgs<T, P>*>(pg_args));
 }
 
+// the horseshoe Polya-Gamma Gibbs sampler: k_pg's layout and LDS (lr_hs.h)
+int launch_hs(const LaunchCfg* cfg, int64_t C, const void* model_args, const void* hs_args) {
+    if (cfg->mode != MODE_LDS || cfg->G != 16) return -3;
+    return launch_capped<&k_hs<T, P>>(cfg, grid_for(C, 16), dim3(256), cfg->lds_bytes, *static_cast<const ModelArgs<T, P>*>(model_args),
+                                      *static_cast<const HsArgs<T, P>*>(hs_args));
+}
+
 const InstTable kTable = {LR_DTYPE, P, (int)(sizeof(kVariants) / sizeof(kVariants[0])), kVariants, &launch_eval,
-                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg, &launch_tall_nuts_t<T, P>, &launch_tall_nuts_t<T, P, true>};
+                          &launch_chain, &launch_tall_partial, &launch_tall_update, nullptr, LR_MFMA_IMAGE_HOOKS, &launch_nuts, &launch_pg, &launch_tall_nuts_t<T, P>, &launch_tall_nuts_t<T, P, true>, &launch_hs};
 
 }  // namespace
 }  // namespace lr

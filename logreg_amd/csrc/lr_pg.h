@@ -156,8 +156,16 @@ __device__ __forceinline__ T pg_draw(T psi, uint64_t seed, uint64_t gchain, uint
 
 template <typename T> __device__ __forceinline__ bool pg_finite(T v) { return (v < T(0) ? -v : v) < T(__builtin_inf()); }
 
-template <typename T, int P>
-__global__ void __launch_bounds__(256) k_pg(ModelArgs<T, P> m, PgArgs<T, P> a) {
+// The hyper-step hooks of pg_sweeps: none for k_pg.  lr_hs.h's HsState (kHyper = true) adds the horseshoe's prior precision to the diagonal
+// of A, updates its scales after the back-solve and writes them out with a kept draw; every call site is under `if constexpr`, so k_pg's
+// code does not depend on it.
+struct PgNoHyper {
+    static constexpr bool kHyper = false;
+};
+
+// `iters x thin` sweeps of every chain: the body of k_pg and of k_hs (lr_hs.h)
+template <typename T, int P, class H>
+__device__ __forceinline__ void pg_sweeps(const ModelArgs<T, P>& m, const PgArgs<T, P>& a, H& h) {
     constexpr int G = 16, NK = (P + 15) / 16, LD = P + kLdsRowPad<T>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int gl = threadIdx.x % G, r = threadIdx.x & 15;
@@ -242,10 +250,12 @@ __global__ void __launch_bounds__(256) k_pg(ModelArgs<T, P> m, PgArgs<T, P> a) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             double diag = 0.0;
+            double prec = ivown[k];
+            if constexpr (H::kHyper) prec = h.precision(k, ivown[k]);
 #pragma unroll
             for (int c = 0; c < P; ++c) {
                 const bool mine = c == r + 16 * k;
-                A[k][c] += mine ? ivown[k] : 0.0;
+                A[k][c] += mine ? prec : 0.0;
                 diag += mine ? A[k][c] : 0.0;
             }
             dj[k] = 1.0 / sqrt(diag);  // (lanes beyond the padded width: 1 / sqrt(0), never read by a lane that matters)
@@ -308,9 +318,11 @@ __global__ void __launch_bounds__(256) k_pg(ModelArgs<T, P> m, PgArgs<T, P> a) {
         n_prop += skip ? 0u : prop_it;
         n_term += skip ? 0u : term_it;
         n_skip += skip ? 1u : 0u;
+        if constexpr (H::kHyper) h.step(skip, x, iter);  // (A is dead here)
 
         if ((sw + 1) % a.thin == 0 && live) {
             const int64_t it = sw / a.thin;
+            if constexpr (H::kHyper) h.keep(it);
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int j = r + 16 * k;
@@ -338,6 +350,12 @@ __global__ void __launch_bounds__(256) k_pg(ModelArgs<T, P> m, PgArgs<T, P> a) {
             cn->skipped += n_skip;
         }
     }
+}
+
+template <typename T, int P>
+__global__ void __launch_bounds__(256) k_pg(ModelArgs<T, P> m, PgArgs<T, P> a) {
+    PgNoHyper h;
+    pg_sweeps<T, P>(m, a, h);
 }
 
 }  // namespace lr

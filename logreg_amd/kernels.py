@@ -6,6 +6,7 @@
     ulKernel(glpi, dt=1e-4, pre=1)               fit-np-ul.py:61-68
     nutsKernel(lpi, glpi, eps=1e-4, dmm=1, max_depth=10)   blackjax.nuts in fit-blackjax-nuts.py:101 (dmm = 1 / pre)
     pgKernel(lpost)                              the tuning-free Gibbs sampler (fit-rjags.R's role): Polya-Gamma augmentation
+    hsKernel(lpost, shrink, global_scale)        the same sampler under the horseshoe prior, for sparse models (no counterpart in the reference)
     mcmc(init, kernel, thin=10, iters=10000, verb=True)   fit-np-hmc.py:89-103
 
 When the callables passed in are the closures of a `LogReg` model (and, for RWMH, a
@@ -36,7 +37,9 @@ NUTS_COUNTERS = np.dtype([("n_leapfrog", "<u8"), ("depth_sum", "<u8"), ("accept_
                           ("max_depth_hits", "<u4")])
 # lr_pg_counters (include/logreg_hip_pg.h) as a NumPy record
 PG_COUNTERS = np.dtype([("proposals", "<u8"), ("series_terms", "<u8"), ("skipped", "<u4"), ("reserved", "<u4")])
-_COUNTERS_BY_KIND = {"nuts": ("nuts_", NUTS_COUNTERS), "pg": ("pg_", PG_COUNTERS)}  # checkpoint prefix, record
+# lr_hs_counters (include/logreg_hip_hs.h)
+HS_COUNTERS = np.dtype([("proposals", "<u8"), ("series_terms", "<u8"), ("skipped", "<u4"), ("clamped", "<u4")])
+_COUNTERS_BY_KIND = {"nuts": ("nuts_", NUTS_COUNTERS), "pg": ("pg_", PG_COUNTERS), "hs": ("hs_", HS_COUNTERS)}  # checkpoint prefix, record
 
 
 # ------------------------------------------------------------------------------------------------
@@ -130,9 +133,9 @@ def _probe_random_walk(rprop, p):
 class FusedKernel:
     """A transition kernel whose whole step runs inside the HIP chain kernel.
 
-    kind in {"rwmh", "mala", "hmc", "ul", "nuts", "pg"}.  Calling it performs ONE iteration on the device with
+    kind in {"rwmh", "mala", "hmc", "ul", "nuts", "pg", "hs"}.  Calling it performs ONE iteration on the device with
     the reference's per-step signature: `kernel(x, ll) -> (x, ll)` for rwmh/mala (the threaded
-    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul/nuts/pg.  Successive calls use
+    log-density, fit-np-mala.py:61-70), `kernel(x) -> x` for hmc/ul/nuts/pg/hs.  Successive calls use
     successive iteration indices of the kernel's own Philox stream.
     """
 
@@ -150,13 +153,18 @@ class FusedKernel:
     def _vec(self, name):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(self.params[name], dtype=np.float64), (self.model.p,)))
 
-    def launch(self, opts: RunOpts, state_ptr, lp_ptr, out_ptr, acc_ptr, counters_ptr=None, depth_ptr=None):
+    def launch(self, opts: RunOpts, state_ptr, lp_ptr, out_ptr, acc_ptr, counters_ptr=None, depth_ptr=None, hyper_ptr=None, scale_ptr=None):
         """One lr_run_<kind> call.  NUTS has no accept counts and no threaded log-density: it takes the per-chain counters
         (lr_nuts_counters) and the optional tree depths of the kept rows instead; the Polya-Gamma sampler its own counters
-        (lr_pg_counters)."""
+        (lr_pg_counters); the horseshoe sampler lr_hs_counters, the hyper-state `[C, 2p+2]` (required) and the optional scales of the
+        kept rows `[iters, C, p+1]`."""
         L = self.model._L
         h = self.model.handle
-        if self.kind == "pg":
+        if self.kind == "hs":
+            mask = np.ascontiguousarray(self.params["shrink"], dtype=np.uint8)
+            prior = _lib.HsPrior(mask.ctypes.data, float(self.params["global_scale"]))
+            check(_lib.bind_hs(L).lr_run_hs(h, C.byref(prior), state_ptr, hyper_ptr, C.byref(opts), out_ptr, scale_ptr, counters_ptr))
+        elif self.kind == "pg":
             check(_lib.bind_pg(L).lr_run_pg(h, state_ptr, C.byref(opts), out_ptr, counters_ptr))
         elif self.kind == "nuts" and self.params.get("inv_metric") is not None:  # dense metric (include/logreg_hip_dense.h)
             v = self.params["inv_metric"]
@@ -194,7 +202,12 @@ class FusedKernel:
         lp = np.ascontiguousarray(np.broadcast_to(np.asarray(-np.inf if ll is None else ll, dtype=np.float64), (Cn,))).copy()
         opts = RunOpts(n_chains=Cn, chain_offset=0, thin=1, iters=1, iter_offset=self._calls, seed=self._seed,
                        group=0, mode=_lib.MODE_AUTO, on_device=0)
-        self.launch(opts, st.ctypes.data, lp.ctypes.data, None, None)
+        hyper_ptr = None
+        if self.kind == "hs":  # the scales travel with the kernel object between calls (a new chain count starts them afresh)
+            if getattr(self, "_hyper", None) is None or self._hyper.shape[0] != Cn:
+                self._hyper = default_hyper(Cn, self.model.p, self.params["global_scale"])
+            hyper_ptr = self._hyper.ctypes.data
+        self.launch(opts, st.ctypes.data, lp.ctypes.data, None, None, hyper_ptr=hyper_ptr)
         self._calls += 1
         xo = st.astype(np.float64)
         if single:
@@ -363,6 +376,45 @@ def pgKernel(lpost):
     return FusedKernel("pg", model)
 
 
+def default_hyper(C, p, global_scale):
+    """The default start of the horseshoe's hyper-state `[C, 2p+2]`: lambda^2 = nu = xi = 1, tau^2 = global_scale^2."""
+    h = np.ones((int(C), 2 * int(p) + 2), dtype=np.float64)
+    h[:, 2 * int(p)] = float(global_scale) ** 2
+    return h
+
+
+def hsKernel(lpost, shrink=None, global_scale=1.0):
+    """The Polya-Gamma Gibbs sampler under the horseshoe prior (Carvalho, Polson & Scott 2010), for sparse models: `pgKernel`'s sweep
+    with the local scales lambda_j and the global scale tau as further Gibbs blocks (include/logreg_hip_hs.h).  Tuning-free like
+    `pgKernel`: no step size, no accept step, no warm-up.
+
+    `shrink`: a boolean mask `[p]` of the coordinates under the horseshoe; the default is every coordinate but 0 (the intercept
+    column).  The model's own Gaussian N(0, pscale_j^2) stays on every coordinate: on a shrunk one it is the slab of the regularised
+    horseshoe, an unshrunk one keeps exactly `pgKernel`'s prior.  `global_scale`: tau0 of tau ~ C+(0, tau0); for p0 expected nonzero
+    effects among m shrunk ones and n rows, Piironen & Vehtari (2017) suggest `p0 / (m - p0) / sqrt(n)` (examples/fit_hs.py).
+    Returns `FusedKernel("hs", model, shrink=mask, global_scale=tau0)`; a `ChainSet` of it carries the hyper-state
+    (`get_hyper` / `set_hyper`), and `mcmc(..., return_info=True)` reports the scales of the kept draws."""
+    model = _model_of(lpost, "lpost")
+    if model is None:
+        raise TypeError("hsKernel needs the `lpost` closure of a LogReg: the Polya-Gamma sampler is built from the model's X, y and prior "
+                        f"scale, not from a log-density it could call (got {type(lpost).__name__})")
+    if shrink is None:
+        mask = np.arange(model.p) > 0
+    else:
+        mask = np.asarray(shrink)
+        if mask.shape != (model.p,) or mask.dtype != np.bool_:
+            raise ValueError(f"shrink must be a boolean mask of shape [{model.p}]; got {mask.dtype} {mask.shape}")
+    if not mask.any():
+        raise ValueError("shrink selects no coordinate: that model is pgKernel's (a LogReg with p = 1 has nothing but its first column)")
+    try:
+        tau0 = float(global_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"global_scale must be a number; got {global_scale!r}") from None
+    if not (np.isfinite(tau0) and tau0 > 0):
+        raise ValueError(f"global_scale must be finite and > 0; got {global_scale!r}")
+    return FusedKernel("hs", model, shrink=mask.copy(), global_scale=tau0)
+
+
 def _numpy_nuts(lpi, glpi, eps, dmm, max_depth, dense=None):
     """The same algorithm on NumPy arrays for arbitrary callables (the generic path: NumPy's global generator, no model arithmetic of
     its own).  `dense` = (Sigma, (s, R, A)): the dense metric -- `c` below is then the matrix Sigma, applied as a product."""
@@ -483,6 +535,9 @@ class ChainSet:
         if kernel.kind in _COUNTERS_BY_KIND:
             self.counters = DeviceArray(m.device, (self.C,), _COUNTERS_BY_KIND[kernel.kind][1])
             self.counters.zero_()
+        self.hyper = None  # horseshoe: the hyper-state [C, 2p+2] (lambda^2, nu, tau^2, xi), float64, moved by every launch
+        if kernel.kind == "hs":
+            self.hyper = DeviceArray.from_host(m.device, default_hyper(self.C, m.p, kernel.params["global_scale"]), dtype=np.float64)
         check(m._L.lr_stream_sync(m.device, None))
         # streaming statistics (enable_stats): device buffer [slots, C, 2, p], batch length, kept samples folded in
         self.stats = None
@@ -495,7 +550,8 @@ class ChainSet:
         opts = RunOpts(n_chains=self.C, group=self.group, mode=self.mode, precision=self.precision, plan_chains=self.plan_chains,
                        chain_offset=self.chain_offset, plan_first=self.plan_first)
         info = _lib.PlanInfo()
-        check(self.model._L.lr_plan_run_info(self.model.handle, _lib.KIND_BY_NAME[self.kernel.kind], C.byref(opts), C.byref(info)))
+        kind = "pg" if self.kernel.kind == "hs" else self.kernel.kind  # (the horseshoe sampler is planned as lr_run_pg is)
+        check(self.model._L.lr_plan_run_info(self.model.handle, _lib.KIND_BY_NAME[kind], C.byref(opts), C.byref(info)))
         plan = {"mode": _lib.MODE_NAMES[info.mode], "group": info.group, "rows_per_lane": info.rows}
         if info.split > 0:  # a run planned in two parts: chains [split, n) of the planned run on wider lane groups
             plan["tail"] = {"from": int(info.split), "mode": _lib.MODE_NAMES[info.tail_mode], "group": info.tail_group,
@@ -516,13 +572,17 @@ class ChainSet:
             self.pivot = np.asarray(pivot, dtype=np.float64).copy()
 
     def advance(self, iters: int, thin: int, keep: bool = True, out: DeviceArray | None = None, stats: bool | None = None,
-                depth: DeviceArray | None = None):
+                depth: DeviceArray | None = None, scales: DeviceArray | None = None):
         """One fused launch: iters*thin iterations per chain.  keep: return the thinned samples `[iters, C, p]`
         (a DeviceArray); stats (default: on when enable_stats was called): fold the kept samples into the
         streaming statistics -- with keep=False nothing of size iters*C*p is ever allocated.
         depth (NUTS): an int8 DeviceArray `[iters, C]` that receives the tree depth of the iteration behind each kept row (negated
-        when it diverged)."""
+        when it diverged).
+        scales (horseshoe): a float64 DeviceArray `[iters, C, p+1]` that receives, with each kept row, lambda_j^2 (1 where unshrunk) and
+        tau^2 at index p."""
         m = self.model
+        if scales is not None and (self.kernel.kind != "hs" or scales.shape != (int(iters), self.C, m.p + 1) or scales.dtype != np.float64):
+            raise ValueError(f"scales= takes a float64 [iters, C, p+1] = [{int(iters)}, {self.C}, {m.p + 1}] array of a horseshoe chain set")
         if keep and out is None:
             out = DeviceArray(m.device, (iters, self.C, m.p), m.np_dtype)
         opts = RunOpts(n_chains=self.C, chain_offset=self.chain_offset, thin=int(thin), iters=int(iters),
@@ -537,7 +597,8 @@ class ChainSet:
         if depth is not None and (self.kernel.kind != "nuts" or depth.shape != (int(iters), self.C) or depth.dtype != np.int8):
             raise ValueError(f"depth= takes an int8 [iters, C] = [{int(iters)}, {self.C}] array of a NUTS chain set")
         self.kernel.launch(opts, self.state.ptr, self.lp.ptr, out.ptr if keep else None, self.acc.ptr,
-                           self.counters.ptr if self.counters is not None else None, depth.ptr if depth is not None else None)
+                           self.counters.ptr if self.counters is not None else None, depth.ptr if depth is not None else None,
+                           **({"hyper_ptr": self.hyper.ptr, "scale_ptr": scales.ptr if scales is not None else None} if self.hyper is not None else {}))
         self.iter_offset += int(iters) * int(thin)
         if use_stats:
             self.stats_kept += int(iters)
@@ -593,14 +654,35 @@ class ChainSet:
 
     def pg_info(self) -> dict:
         """Polya-Gamma: per-chain proposals, series_terms and skipped (lr_pg_counters) over the iterations run so far, and the two
-        ratios to rows x iterations (`proposals_per_draw`: theory <= 1.0009; skipped iterations draw nothing)."""
-        if self.kernel.kind != "pg":
+        ratios to rows x iterations (`proposals_per_draw`: theory <= 1.0009; skipped iterations draw nothing).  A horseshoe chain set
+        adds `clamped` (lr_hs_counters)."""
+        if self.kernel.kind not in ("pg", "hs"):
             raise ValueError("pg_info is for Polya-Gamma chain sets")
         c = self.get_counters()
         draws = np.maximum((self.iter_offset - c["skipped"].astype(np.int64)) * self.model.n, 1)
-        return {"proposals": c["proposals"].astype(np.int64), "series_terms": c["series_terms"].astype(np.int64),
+        info = {"proposals": c["proposals"].astype(np.int64), "series_terms": c["series_terms"].astype(np.int64),
                 "skipped": c["skipped"].astype(np.int64), "proposals_per_draw": c["proposals"] / draws,
                 "series_terms_per_draw": c["series_terms"] / draws}
+        if self.kernel.kind == "hs":
+            info["clamped"] = c["clamped"].astype(np.int64)
+        return info
+
+    def get_hyper(self) -> np.ndarray:
+        """Horseshoe: the hyper-state `[C, 2p+2]` (lambda^2 `[p]`, nu `[p]`, tau^2, xi per chain), float64."""
+        if self.hyper is None:
+            raise ValueError("the hyper-state exists for horseshoe chain sets only")
+        self.sync()
+        return self.hyper.to_host()
+
+    def set_hyper(self, hyper):
+        """Horseshoe: replace the hyper-state; `[2p+2]` or `[C, 2p+2]`, every entry finite and in [1e-100, 1e100]."""
+        if self.hyper is None:
+            raise ValueError("the hyper-state exists for horseshoe chain sets only")
+        h = np.ascontiguousarray(np.broadcast_to(np.asarray(hyper, dtype=np.float64), (self.C, 2 * self.model.p + 2)))
+        if not np.all((h >= _lib.HS_MIN) & (h <= _lib.HS_MAX)):
+            raise ValueError(f"every entry of the hyper-state must be finite and in [{_lib.HS_MIN:g}, {_lib.HS_MAX:g}]")
+        self.sync()
+        self.hyper.copy_from(h)
 
     # -- checkpoint / resume (the reference has none: a run is all-or-nothing).  Because the random
     # stream is counter-based, (state, threaded ll, iteration counter, seed, chain offset) IS the
@@ -624,6 +706,8 @@ class ChainSet:
             cn = self.counters.to_host()
             prefix, rec = _COUNTERS_BY_KIND[self.kernel.kind]
             ck.update({prefix + f: cn[f].copy() for f in rec.names})
+        if self.hyper is not None:  # horseshoe: the scales are part of the sampler's state
+            ck.update(hyper=self.hyper.to_host())
         if self.stats is not None:  # the statistics window travels with the run
             ck.update(stats=self.stats.to_host(), stats_batch=np.int64(self.stats_batch), stats_kept=np.int64(self.stats_kept),
                       stats_pivot=np.asarray(self.pivot, dtype=np.float64))
@@ -671,6 +755,10 @@ class ChainSet:
                 for f in rec.names:
                     cn[f] = ckpt[prefix + f]
                 cs.counters.copy_from(cn)
+        if cs.hyper is not None:
+            if "hyper" not in ckpt:
+                raise ValueError("checkpoint of a horseshoe chain set without its hyper-state")
+            cs.set_hyper(ckpt["hyper"])
         if "stats" in ckpt:
             st = np.asarray(ckpt["stats"], dtype=np.float64)
             cs.enable_stats(int(ckpt["stats_batch"]), st.shape[0], pivot=ckpt["stats_pivot"])
@@ -689,7 +777,7 @@ def _auto_chunk(kernel: FusedKernel, C: int, thin: int, iters: int, evals_per_it
         evals = evals_per_iter if evals_per_iter else 2 ** int(kernel.params["max_depth"]) - 1
     else:
         # (a Polya-Gamma sweep: n draws and n p (p + 1) / 2 multiply-adds -- priced as p / 2 + 8 passes over the data)
-        evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1, "pg": kernel.model.p / 2 + 8}[kernel.kind]
+        evals = {"hmc": kernel.params.get("l", 1), "mala": 1, "ul": 1, "rwmh": 1, "pg": kernel.model.p / 2 + 8, "hs": kernel.model.p / 2 + 8}[kernel.kind]
     work_per_kept = max(1, int(thin * evals * kernel.model.n * kernel.model.p))
     return int(max(1, min(iters, 2_000_000_000 // work_per_kept)))
 
@@ -779,6 +867,10 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     `return_info=True`, the info dict -- gains `"check": check.result()` (per group the observed and replicated counts with their tail
     probabilities, the deviance check, the per-row frequency of ones).  Chains, states, statistics and accept counts are those of the same
     call without it.
+    An `hsKernel` (the horseshoe Polya-Gamma sampler) reports what a `pgKernel` does, plus `clamped` and the final hyper-state `hyper`
+    `[C, 2p+2]`; a sample-returning run with `return_info=True` adds the scales of the kept draws, `local_scale2` `[iters, C, p]`
+    (lambda_j^2; 1 where unshrunk) and `global_scale2` `[iters, C]` (tau^2).  `bridge=` is refused: the evidence a `Bridge` computes is
+    under the model's Gaussian prior, not the horseshoe.
     A `pgKernel` (the Polya-Gamma Gibbs sampler) has no accept count: `return_info=True` and `summary_only=True` report its per-chain
     counters instead (`proposals`, `series_terms`, `skipped` and the two ratios of `ChainSet.pg_info`); `accept_rate` is the share of
     sweeps that were not skipped.
@@ -794,6 +886,9 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         for name in given:
             raise ValueError(f"{name}= needs a fused kernel (the closures of a LogReg)")
         return _mcmc_generic(init, kernel, thin, iters, verb)
+    if kernel.kind == "hs" and bridge is not None:
+        raise ValueError("bridge= is refused with an hsKernel: the evidence a Bridge computes is under the model's Gaussian prior, not "
+                         "the horseshoe the chains sample from")
     if predictive is not None and getattr(predictive, "model", None) is not kernel.model:
         raise ValueError("predictive= must be a PosteriorPredictive of the kernel's own model")
     init = np.asarray(init, dtype=np.float64)
@@ -856,25 +951,33 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
         if nuts:  # the mean acceptance statistic in place of an acceptance rate
             ni = cs.nuts_info()
             res.update(ni, accept_rate=float(np.mean(ni["mean_accept_stat"])))
-        elif kernel.kind == "pg":  # a Gibbs sweep always moves, unless it was skipped
+        elif kernel.kind in ("pg", "hs"):  # a Gibbs sweep always moves, unless it was skipped
             gi = cs.pg_info()
             res.update(gi, accept_rate=float(1.0 - gi["skipped"].sum() / (cs.C * iters * thin)))
+            if kernel.kind == "hs":
+                res.update(hyper=cs.get_hyper())
         else:
             res.update(accept_rate=float(cs.get_accepts().sum() / (cs.C * iters * thin)))
         res.update(batch=batch, seed=seed, plan=cs.plan(), state=cs.get_state())
         attach(res)
         return res
     mat = np.empty((iters, cs.C, m.p), dtype=m.np_dtype)
+    want_scales = kernel.kind == "hs" and return_info
+    scale_mat = np.empty((iters, cs.C, m.p + 1), dtype=np.float64) if want_scales else None
     if verb:
         print(str(iters) + " iterations")
     done = 0
     while done < iters:
         k = min(chunk, iters - done)
-        out = cs.advance(k, thin, keep=True)
+        sc = DeviceArray(m.device, (k, cs.C, m.p + 1), np.float64) if want_scales else None
+        out = cs.advance(k, thin, keep=True, scales=sc)
         fold(out)
         cs.sync()
         mat[done:done + k] = out.to_host()
         out.free()
+        if sc is not None:
+            scale_mat[done:done + k] = sc.to_host()
+            sc.free()
         done += k
         chunk = rechunk()
         if verb:
@@ -885,8 +988,11 @@ def mcmc(init, kernel, thin=10, iters=10000, verb=True, *, seed=None, chunk=None
     if return_info:
         if nuts:  # per chain: n_leapfrog, divergent, max_depth_hits, mean_depth, mean_accept_stat
             info = {"state": cs.get_state(), "seed": seed, "plan": cs.plan(), "iterations": iters * thin, **cs.nuts_info()}
-        elif kernel.kind == "pg":  # per chain: proposals, series_terms, skipped and the two ratios
+        elif kernel.kind in ("pg", "hs"):  # per chain: proposals, series_terms, skipped and the two ratios
             info = {"state": cs.get_state(), "seed": seed, "plan": cs.plan(), "iterations": iters * thin, **cs.pg_info()}
+            if kernel.kind == "hs":
+                local = scale_mat[:, :, :m.p]
+                info.update(hyper=cs.get_hyper(), local_scale2=local[:, 0] if single else local, global_scale2=scale_mat[:, 0, m.p] if single else scale_mat[:, :, m.p])
         else:
             info = {"accepts": cs.get_accepts(), "state": cs.get_state(), "ll": cs.get_ll(), "seed": seed,
                     "plan": cs.plan(), "iterations": iters * thin}
